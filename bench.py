@@ -6,9 +6,15 @@ A step = one damped-Jacobi sweep (residual + update, 7-point stencil, fp64, LINE
 of the 512^3 grid of BASELINE config #3 (512^3 lattice updates). The K timed sweeps run exactly as
 the solver runs its 2+2 smoothing: in fused pairs (gs_jacobi_sweep2, temporal blocking: one read of
 v and f and one write per pair), an odd last sweep alone. value = lattice updates of all ranks /
-max-over-ranks wall time (MLUPS). Inputs are resident in HBM before the timed region. The one-sweep
-kernel is also timed on its own ("single_sweep_kernel"), and the V-cycle wall time (512^3, 2+2,
-including the 8-byte norm readback) is measured after the timed region ("vcycle").
+max-over-ranks wall time (MLUPS). Inputs are resident in HBM before the timed region.
+
+A plain run does only that: it builds the grid, warms up, times the K sweeps, writes their result with
+--dump-outputs DIR, and prints the line. With --full every other leg runs after the timed region and fills
+its field of the line (null otherwise): the one-sweep kernel on its own ("single_sweep_kernel"), the
+streaming ceilings, the V-cycle wall time (512^3, 2+2, including the 8-byte norm readback; "vcycle"), the
+Newton solve, BASELINE configs #2 and #5, the CPU baseline, and at N > 1 the exchange-free pair, the RCCL
+CTA-budget comparison, the transports and the same-job strong-scaling denominator. The legs' own options
+(--vcycles, --cpu-sweeps, --config5, ...) size or skip them under --full and are ignored without it.
 
 Multi-GPU (torchrun, one process per GPU): the grid is Z-slab partitioned over RCCL (xGMI), ghost
 planes exchanged every sweep on a second stream while the interior planes are swept; weak scaling
@@ -26,6 +32,7 @@ cpu_baseline: the reference's own CpuSolver::jacobi (oracle/_ref/ref_probe, comp
 /root/reference/src/cpu) on this host's cores, a bounded sample of the same workload.
 """
 import argparse
+import ctypes as C
 import json
 import math
 import os
@@ -33,6 +40,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -65,7 +73,19 @@ def parse():
     ap.add_argument("--cta-ab", default="16,64",
                     help="N > 1: after the headline, time the same sweeps on fresh RCCL communicators with these "
                          "CTA budgets (ncclConfig_t::minCTAs = maxCTAs), interleaved twice ('' skips)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg (one-sweep kernel, streaming ceilings, V-cycle, "
+                         "Newton, configs #2 and #5, CPU baseline, the RCCL legs at N > 1); without it those legs' "
+                         "options are ignored and their fields of the line are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="the timed sweeps start from the initial iterate (v = 0) and, after them, the level-0 iterate "
+                         "they produced is written to DIR/v.npy (DIR/v_rank<r>.npy at N > 1) as float64: the owned "
+                         "points, or a fixed seeded sample of them (see dump_outputs)")
+    a = ap.parse_args()
+    if not a.full:  # a plain run: set up, warm up, the timed sweeps, the line
+        a.vcycles = a.cpu_sweeps = a.cpu_vcycles = a.config5 = a.config2 = a.newton_iters = 0
+        a.cta_ab = ""
+    return a
 
 
 def pmc_traffic(n):
@@ -569,6 +589,56 @@ def ramp_sweeps(run, ramp_ms, any_rank, chunk=40):
     return done, (time.perf_counter() - tw) * 1e3
 
 
+DUMP_SEED = 20240611
+DUMP_MAX_POINTS = 4 << 20  # 32 MiB of float64
+
+
+def reset_iterate(grid):
+    """--dump-outputs: level 0's iterate back to the grid's initial one (v = 0, ghost layer included), so that the
+    timed sweeps start from the same input in every run however many sweeps the wall-clock ramp ran before them.
+    A device-side fill on the grid's stream (no host copy: the GPU stays busy between the ramp and the sweeps) of
+    exactly the span gs_grid_upload writes: rows of nx+2 values at pitch ldy, from the first row to the last row's end
+    (a Z-slab's second ghost planes lie outside it and keep what the last exchange left: N = 1 is what is identical
+    from run to run)."""
+    L = grid.getLevel(0).geom
+    ptr = gsv.driver().gs_grid_field(grid.handle, 0, gsv.FIELDS["v"])
+    if not ptr:
+        raise gsv.GpuSolveError("level 0 has no iterate")
+    rows = (int(L.ny) + 2) * (int(L.nz) + 2)
+    elems = int(L.ldy) * (rows - 1) + int(L.nx) + 2
+
+    class Span:  # the field's memory as torch sees foreign device memory
+        __cuda_array_interface__ = {"shape": (elems,), "typestr": "<f8", "version": 2,
+                                    "data": (int(ptr), False)}
+
+    with torch.cuda.stream(torch.cuda.ExternalStream(grid.stream())):
+        torch.as_tensor(Span(), device="cuda").zero_()
+
+
+def dump_outputs(grid, out_dir, rank, world):
+    """Writes what the timed sweeps left in level 0's iterate (this rank's owned points, the ghost layer dropped) to
+    out_dir/v.npy (v_rank<r>.npy at N > 1) as float64. Up to DUMP_MAX_POINTS points the whole block is written, indexed
+    [z][y][x]; a larger block as a 1-D sample of DUMP_MAX_POINTS points at flat [z][y][x] indices drawn (with
+    replacement, in drawing order) from numpy's default_rng(DUMP_SEED): the same points for the same grid in every
+    run and every build."""
+    L = grid.getLevel(0).geom
+    host = np.empty((L.nz + 2, L.ny + 2, L.nx + 2), dtype=np.float64)
+    if gsv.driver().gs_grid_download(grid.handle, 0, gsv.FIELDS["v"], host.ctypes.data_as(C.POINTER(C.c_double))):
+        raise gsv.GpuSolveError(gsv.driver().gs_last_error().decode())
+    pts = int(L.nx) * int(L.ny) * int(L.nz)
+    if pts <= DUMP_MAX_POINTS:
+        out = np.ascontiguousarray(host[1:-1, 1:-1, 1:-1])
+    else:
+        idx = np.random.default_rng(DUMP_SEED).integers(0, pts, size=DUMP_MAX_POINTS)
+        z, y, x = np.unravel_index(idx, (L.nz, L.ny, L.nx))
+        out = host[z + 1, y + 1, x + 1]
+    os.makedirs(out_dir, exist_ok=True)
+    name = "v.npy" if world == 1 else f"v_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), out)
+    return {"file": name, "shape": list(out.shape), "dtype": "float64",
+            "sample": None if pts <= DUMP_MAX_POINTS else f"default_rng({DUMP_SEED}).integers(0, {pts}, {DUMP_MAX_POINTS})"}
+
+
 def main():
     a = parse()
     # stdout carries exactly the one JSON line: anything the libraries print there (RCCL writes a version
@@ -589,7 +659,7 @@ def main():
         cpp = gsv.driver().gs_rccl_channels_per_peer_hint(-1)
         if cpp > 0:
             os.environ.setdefault("NCCL_NCHANNELS_PER_PEER", str(cpp))
-        rccl_log = rccl_debug_setup()
+        rccl_log = rccl_debug_setup() if a.full else None
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local % max(1, torch.cuda.device_count())))
 
     def barrier():
@@ -624,9 +694,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return t.item() > 0
 
-    def timed_window(g, warmup, ramp_ms, steps):
+    def timed_window(g, warmup, ramp_ms, steps, reset=False):
         """Untimed warm-up + agreed ramp, then exactly `steps` sweeps bracketed by a barrier and a device
-        synchronisation on both sides, HIP events on the grid's own stream. Returns (max-over-ranks wall s,
+        synchronisation on both sides, HIP events on the grid's own stream; with `reset`, the iterate is set
+        back to the initial one between the ramp and the sweeps. Returns (max-over-ranks wall s,
         this rank's wall s, this rank's average pass ms, ramp sweeps, warm-up ms)."""
         gstream = torch.cuda.ExternalStream(g.stream())
 
@@ -638,10 +709,15 @@ def main():
             gsweeps(k)
             g.sync()
 
+        if reset:  # torch's one-off costs of the fill (its first launch) are paid here, not after the ramp
+            reset_iterate(g)
+            torch.cuda.synchronize()
         tw = time.perf_counter()
         grun(warmup)
         rmp, _ = ramp_sweeps(grun, max(0.0, ramp_ms - (time.perf_counter() - tw) * 1e3), any_rank)
         wms = (time.perf_counter() - tw) * 1e3
+        if reset:
+            reset_iterate(g)
         barrier()
         torch.cuda.synchronize()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -660,13 +736,15 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return t.item(), own, kms, rmp, wms
 
-    elapsed, own_elapsed, kernel_ms, ramp, warmup_ms = timed_window(grid, a.warmup, a.ramp_ms, a.steps)
+    elapsed, own_elapsed, kernel_ms, ramp, warmup_ms = timed_window(grid, a.warmup, a.ramp_ms, a.steps,
+                                                                    reset=a.dump_outputs is not None)
     passes = (a.steps // 2 + a.steps % 2) if fused else a.steps
+    dumped = dump_outputs(grid, a.dump_outputs, rank, world) if a.dump_outputs is not None else None
 
     multi = None
     if world > 1:  # per-rank view of the timed window, and the pair's cost without its exchange
         try:
-            local = slab_local_pair_ms(grid, rank, world, max(4, passes))
+            local = slab_local_pair_ms(grid, rank, world, max(4, passes)) if a.full else float("nan")
         except Exception:  # noqa: BLE001 (diagnostic only)
             local = float("nan")
         import ctypes as C
@@ -705,7 +783,7 @@ def main():
                          "flight"}
 
     single = ceilings = ceiling = None
-    if world == 1:
+    if world == 1 and a.full:
         single = single_sweep_timing(grid, dims, a.steps)
         ceilings = stream_ceilings((int(dims[0]) * dims[1] * dims[2]) & ~1)  # (the probe streams element pairs)
         ceiling = ceilings["triad"]
@@ -787,7 +865,7 @@ def main():
                                                       "pair_ms_max_rank": round(km.item(), 4)})
 
     transports = None
-    if world > 1 and not rccl_log:
+    if world > 1 and a.full and not rccl_log:
         transports = {"error": "NCCL_DEBUG_FILE preset without NCCL_DEBUG=INFO: no connection log to parse"}
     if world > 1 and rccl_log:
         mine = rccl_transports(rccl_log)
@@ -938,6 +1016,8 @@ def main():
             "config2": c2,
             "speedup_vs_1gpu_same_grid": speedup,
             "cpu_baseline": cpu,
+            "full": bool(a.full),
+            "dump_outputs": dumped,
             "kernel_build": gsv.build_info(),
         }
         if pmc:

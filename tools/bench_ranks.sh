@@ -15,7 +15,7 @@ for r in $(seq 0 $((N - 1))); do
   NCCL_HOSTID=gs-bench-rank-$r NCCL_SOCKET_IFNAME=lo NCCL_IB_DISABLE=1 GS_COMM_INIT_TIMEOUT_S=90 GS_COMM_TIMEOUT_S=60 \
   WORLD_SIZE=$N RANK=$r LOCAL_RANK=0 LOCAL_WORLD_SIZE=$N MASTER_ADDR=127.0.0.1 MASTER_PORT=$PORT \
     timeout -k 10 300 ${PROF:+rocprofv3 --kernel-trace -d "$OUT/prof_r$r" -o run --output-format csv --} \
-    python bench.py --gpus "$N" --size "$SIZE" --steps 10 --warmup 2 "$@" \
+    python bench.py --full --gpus "$N" --size "$SIZE" --steps 10 --warmup 2 "$@" \
     > "$OUT/rank$r.json" 2> "$OUT/rank$r.err" &
   pids+=($!)
 done

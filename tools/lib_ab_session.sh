@@ -12,7 +12,7 @@ trap restore EXIT INT TERM
 for r in $(seq 1 $R); do
   for v in new alt; do
     if [ $v = new ]; then cp $O/new.so $L/libgpusolve_hip.so; else cp $ALT $L/libgpusolve_hip.so; fi
-    timeout -k 10 300 python bench.py --steps 20 --warmup 5 --vcycles 10 --cpu-sweeps 0 --newton-iters $NI --config5 0 \
+    timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --vcycles 10 --cpu-sweeps 0 --newton-iters $NI --config5 0 \
       > $O/b_${v}_r$r.json 2> $O/b_${v}_r$r.err || { tail $O/b_${v}_r$r.err; exit 1; }
     python -c "
 import json; d=json.load(open('$O/b_${v}_r$r.json')); k=d['vcycle']['level0_kernels']

@@ -8,7 +8,7 @@ for r in $(seq 1 $R); do
   for spec in "$@"; do
     v=${spec%%:*}; envs=${spec#*:}
     env $envs timeout -k 10 300 python tools/newton_kprobe.py 2 10 512 > $O/kp_${v}_r$r.json 2> $O/kp_${v}_r$r.err || { tail $O/kp_${v}_r$r.err; exit 1; }
-    env $envs timeout -k 10 300 python bench.py --steps 20 --warmup 5 --vcycles 10 --cpu-sweeps 0 --newton-iters $NI --config5 0 \
+    env $envs timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --vcycles 10 --cpu-sweeps 0 --newton-iters $NI --config5 0 \
       > $O/b_${v}_r$r.json 2> $O/b_${v}_r$r.err || { tail $O/b_${v}_r$r.err; exit 1; }
     python -c "
 import json; d=json.load(open('$O/b_${v}_r$r.json')); k=d['vcycle']['level0_kernels']

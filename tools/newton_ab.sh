@@ -6,7 +6,7 @@ set -o pipefail
 O=gpurun_out/${1:-nab}; VAR=$2; R=$3; shift 3; mkdir -p $O; export TMPDIR=/tmp
 for r in $(seq 1 $R); do
   for v in "$@"; do
-    env $VAR=$v timeout -k 10 300 python bench.py --steps 4 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 \
+    env $VAR=$v timeout -k 10 300 python bench.py --full --steps 4 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 \
       --newton-iters 2 > $O/b_${v}_r$r.json 2> $O/b_${v}_r$r.err || { tail $O/b_${v}_r$r.err; exit 1; }
     python -c "import json; d=json.load(open('$O/b_${v}_r$r.json')); print('$VAR=$v r$r newton ms/iter', d['newton']['ms_per_iteration'], d['newton']['residuals'])"
   done

@@ -17,9 +17,9 @@ for rep in 1 2; do
   for sw in default GS_NO_NEWTON_FUSED_UPDATE; do
     step "bench newton $sw rep $rep"
     if [ "$sw" = default ]; then
-      timeout -k 10 300 python bench.py --steps 4 --warmup 2 --cpu-sweeps 0 --vcycles 0 --config5 0 --newton-iters 2 > "$OUT/bench_${sw}_$rep.json" 2> "$OUT/bench_${sw}_$rep.err" || { tail -20 "$OUT/bench_${sw}_$rep.err"; exit 1; }
+      timeout -k 10 300 python bench.py --full --steps 4 --warmup 2 --cpu-sweeps 0 --vcycles 0 --config5 0 --newton-iters 2 > "$OUT/bench_${sw}_$rep.json" 2> "$OUT/bench_${sw}_$rep.err" || { tail -20 "$OUT/bench_${sw}_$rep.err"; exit 1; }
     else
-      env $sw=1 timeout -k 10 300 python bench.py --steps 4 --warmup 2 --cpu-sweeps 0 --vcycles 0 --config5 0 --newton-iters 2 > "$OUT/bench_${sw}_$rep.json" 2> "$OUT/bench_${sw}_$rep.err" || { tail -20 "$OUT/bench_${sw}_$rep.err"; exit 1; }
+      env $sw=1 timeout -k 10 300 python bench.py --full --steps 4 --warmup 2 --cpu-sweeps 0 --vcycles 0 --config5 0 --newton-iters 2 > "$OUT/bench_${sw}_$rep.json" 2> "$OUT/bench_${sw}_$rep.err" || { tail -20 "$OUT/bench_${sw}_$rep.err"; exit 1; }
     fi
     python -c "import json,sys; d=json.load(open('$OUT/bench_${sw}_$rep.json')); print('$sw', d['newton']['ms_per_iteration'], d['newton']['residuals'])"
   done

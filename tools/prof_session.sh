@@ -13,10 +13,10 @@ step() { echo "[$(date +%T)] $*"; }
 if [ "$2" != "pmconly" ]; then
 step rocprof-bench
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-    python bench.py --steps 20 --warmup 5 --cpu-sweeps 0 --newton-iters 0 --vcycles 0 > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.err" || { tail -20 "$OUT/bench_prof.err"; exit 1; }
+    python bench.py --full --steps 20 --warmup 5 --cpu-sweeps 0 --newton-iters 0 --vcycles 0 > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.err" || { tail -20 "$OUT/bench_prof.err"; exit 1; }
 step rocprof-vcycle
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_vc" -o run --output-format csv -- \
-    python bench.py --steps 2 --warmup 2 --ramp-ms 0 --cpu-sweeps 0 --newton-iters 0 --vcycles 10 > "$OUT/bench_vc.json" 2> "$OUT/bench_vc.err" || { tail -20 "$OUT/bench_vc.err"; exit 1; }
+    python bench.py --full --steps 2 --warmup 2 --ramp-ms 0 --cpu-sweeps 0 --newton-iters 0 --vcycles 10 > "$OUT/bench_vc.json" 2> "$OUT/bench_vc.err" || { tail -20 "$OUT/bench_vc.err"; exit 1; }
 python tools/vc_breakdown.py "$(find $OUT/prof_vc -name "*kernel_trace.csv" -print -quit)" 40 > "$OUT/vc_breakdown.txt" || true
 cat "$OUT/vc_breakdown.txt"
 fi

@@ -10,7 +10,7 @@ GS_RB_ZC=172 timeout -k 10 600 python -u -m pytest tests/test_gpu_newton_update.
 tail -1 "$OUT/pytest.log"
 for r in 1 2 3; do
   for v in 0 64 172; do
-    GS_RB_ZC=$v timeout -k 10 300 python bench.py --steps 4 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
+    GS_RB_ZC=$v timeout -k 10 300 python bench.py --full --steps 4 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
       > "$OUT/n_${v}_r$r.json" 2> "$OUT/n_${v}_r$r.err" || { tail "$OUT/n_${v}_r$r.err"; exit 1; }
     python -c "import json; d=json.load(open('$OUT/n_${v}_r$r.json')); print('GS_RB_ZC=$v r$r newton', d['newton']['ms_per_iteration'], 'k_rb', d['single_sweep_kernel']['ms'])"
   done

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 step() { echo "[$(date +%T)] $*"; }
 nrun() { # tag size env...
   local tag=$1 size=$2; shift 2
-  env "$@" timeout -k 10 300 python bench.py --size $size --steps 4 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
+  env "$@" timeout -k 10 300 python bench.py --full --size $size --steps 4 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
     > "$OUT/$tag.json" 2> "$OUT/$tag.err" || { tail "$OUT/$tag.err"; exit 1; }
   python -c "import json; d=json.load(open('$OUT/$tag.json')); print('$tag', d['newton']['ms_per_iteration'])"
 }
@@ -18,11 +18,11 @@ step pytest-gpu-full
 timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > "$OUT/pytest.log" 2>&1 || { tail -40 "$OUT/pytest.log"; exit 1; }
 tail -1 "$OUT/pytest.log"
 step bench-driver-flags
-timeout -k 10 400 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 400 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 python tools/bench_brief.py "$OUT/bench.json" || true
 step bench-rocprof-stats
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof_bench" -o run --output-format csv -- \
-    python bench.py --steps 20 --warmup 20 --cpu-sweeps 0 > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err" || { tail -20 "$OUT/prof_bench.err"; exit 1; }
+    python bench.py --full --steps 20 --warmup 20 --cpu-sweeps 0 > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err" || { tail -20 "$OUT/prof_bench.err"; exit 1; }
 step newton-pro-threshold
 for r in 1 2; do
   for s in 256 512; do

@@ -22,12 +22,12 @@ for r in 1 2 3; do
   done
 done
 step newton-1024
-timeout -k 10 400 python bench.py --size 1024 --steps 2 --warmup 2 --vcycles 2 --cpu-sweeps 0 --config5 0 --newton-iters 1 \
+timeout -k 10 400 python bench.py --full --size 1024 --steps 2 --warmup 2 --vcycles 2 --cpu-sweeps 0 --config5 0 --newton-iters 1 \
   > "$OUT/newton1024.json" 2> "$OUT/newton1024.err" || { tail -20 "$OUT/newton1024.err"; exit 1; }
 python -c "import json; d=json.load(open('$OUT/newton1024.json')); print('1024^3 newton', d['newton']); print('vcycle', d['vcycle']['ms'])"
 step newton-1024-trace
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof_n1024" -o run --output-format csv -- \
-  python bench.py --size 1024 --steps 2 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 1 > "$OUT/prof_n1024.json" 2> "$OUT/prof_n1024.err" || { tail -20 "$OUT/prof_n1024.err"; exit 1; }
+  python bench.py --full --size 1024 --steps 2 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 1 > "$OUT/prof_n1024.json" 2> "$OUT/prof_n1024.err" || { tail -20 "$OUT/prof_n1024.err"; exit 1; }
 python tools/kernel_agg.py "$(find $OUT/prof_n1024 -name '*kernel_trace.csv' -print -quit)" > "$OUT/n1024_agg.txt" || true
 head -25 "$OUT/n1024_agg.txt" || true
 step done

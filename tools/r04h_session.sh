@@ -20,7 +20,7 @@ for v in 0 1; do
 done
 nrun() { # tag env...
   local tag=$1; shift
-  env "$@" timeout -k 10 400 python bench.py --size 1023 --steps 2 --warmup 2 --vcycles 2 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
+  env "$@" timeout -k 10 400 python bench.py --full --size 1023 --steps 2 --warmup 2 --vcycles 2 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
     > "$OUT/$tag.json" 2> "$OUT/$tag.err" || { tail "$OUT/$tag.err"; exit 1; }
   python -c "import json; d=json.load(open('$OUT/$tag.json')); print('$tag', d['newton']['ms_per_iteration'], d['newton']['residuals'], 'vcycle', d['vcycle']['ms'])"
 }

@@ -17,14 +17,14 @@ step fuzz
 GS_FUZZ_N=600 GS_FUZZ_SEED=20261018 timeout -k 10 600 python -u -m pytest tests/test_gpu_fuzz.py -m gpu -x -q --timeout 300 --timeout-method thread > "$OUT/fuzz.log" 2>&1 || { tail -30 "$OUT/fuzz.log"; exit 1; }
 tail -1 "$OUT/fuzz.log"
 step bench-driver-flags
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 python tools/bench_brief.py "$OUT/bench.json" || true
 step bench-rocprof-stats
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof_bench" -o run --output-format csv -- \
-    python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-sweeps 0 > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err" || { tail -20 "$OUT/prof_bench.err"; exit 1; }
+    python bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-sweeps 0 > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err" || { tail -20 "$OUT/prof_bench.err"; exit 1; }
 step newton-512
 for r in 1 2 3; do
-  timeout -k 10 300 python bench.py --steps 4 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 2 > "$OUT/newton_r$r.json" 2> "$OUT/newton_r$r.err" || { tail "$OUT/newton_r$r.err"; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 4 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 2 > "$OUT/newton_r$r.json" 2> "$OUT/newton_r$r.err" || { tail "$OUT/newton_r$r.err"; exit 1; }
   python -c "import json; d=json.load(open('$OUT/newton_r$r.json')); print('newton r$r', d['newton']['ms_per_iteration'])"
 done
 step ranks8

@@ -17,7 +17,7 @@ timeout -k 10 300 python tools/newton_kprobe.py 2 3 1023 > "$OUT/kp.json" 2> "$O
 python -c "import json; d=json.load(open('$OUT/kp.json'))['ms']; print({k: min(x) for k, x in d.items() if isinstance(x, list)})"
 step newton-1023
 for r in 1 2; do
-  timeout -k 10 400 python bench.py --size 1023 --steps 2 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
+  timeout -k 10 400 python bench.py --full --size 1023 --steps 2 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
     > "$OUT/n1023_r$r.json" 2> "$OUT/n1023_r$r.err" || { tail "$OUT/n1023_r$r.err"; exit 1; }
   python -c "import json; d=json.load(open('$OUT/n1023_r$r.json')); print('1023 r$r', d['newton']['ms_per_iteration'], d['newton']['residuals'])"
 done

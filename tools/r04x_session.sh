@@ -11,7 +11,7 @@ timeout -k 10 900 python -u -m pytest tests/test_gpu_switches.py tests/test_gpu_
 tail -1 "$OUT/pytest.log"
 for r in 1 2 3; do
   for v in 0 32; do
-    GS_RR_ZC_BIG=$v timeout -k 10 300 python bench.py --steps 4 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
+    GS_RR_ZC_BIG=$v timeout -k 10 300 python bench.py --full --steps 4 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
       > "$OUT/n_${v}_r$r.json" 2> "$OUT/n_${v}_r$r.err" || { tail "$OUT/n_${v}_r$r.err"; exit 1; }
     python -c "import json; d=json.load(open('$OUT/n_${v}_r$r.json')); print('GS_RR_ZC_BIG=$v r$r newton', d['newton']['ms_per_iteration'])"
   done

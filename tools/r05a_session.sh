@@ -16,13 +16,13 @@ step pytest-gpu-full
 timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread --maxfail 20 > "$OUT/pytest.log" 2>&1; rc=$?
 tail -25 "$OUT/pytest.log"; fatal $rc
 step bench-driver-flags
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 python tools/bench_brief.py "$OUT/bench.json" || true
 step newton-ab
 for r in 1 2; do
   for v in b ref; do
     if [ $v = ref ]; then export GS_NO_NEWTON_B=1; else unset GS_NO_NEWTON_B; fi
-    timeout -k 10 300 python bench.py --steps 4 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
+    timeout -k 10 300 python bench.py --full --steps 4 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
       > "$OUT/newton_${v}_r$r.json" 2> "$OUT/newton_${v}_r$r.err" || { tail "$OUT/newton_${v}_r$r.err"; exit 1; }
     python -c "import json; d=json.load(open('$OUT/newton_${v}_r$r.json')); print('newton $v r$r', d['newton']['ms_per_iteration'], d['newton']['residuals'])"
   done
@@ -30,7 +30,7 @@ done
 unset GS_NO_NEWTON_B
 step vcycle-trace
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_vc" -o run --output-format csv -- \
-    python bench.py --steps 2 --warmup 2 --ramp-ms 0 --cpu-sweeps 0 --newton-iters 0 --config5 0 --vcycles 10 > "$OUT/bench_vc.json" 2> "$OUT/bench_vc.err" || { tail -20 "$OUT/bench_vc.err"; exit 1; }
+    python bench.py --full --steps 2 --warmup 2 --ramp-ms 0 --cpu-sweeps 0 --newton-iters 0 --config5 0 --vcycles 10 > "$OUT/bench_vc.json" 2> "$OUT/bench_vc.err" || { tail -20 "$OUT/bench_vc.err"; exit 1; }
 VT=$(find "$OUT/prof_vc" -name '*kernel_trace.csv' -print -quit)
 python tools/gap_report.py "$VT" vcycle512 --json "$OUT/gaps_vcycle.json"
 step newton-trace

@@ -18,7 +18,7 @@ step ab
 for r in 1 2; do
   for v in def ng1 bf0; do
     case $v in def) E="GS_NONE=1";; ng1) E="GS_RR_NG=1";; bf0) E="GS_NEWTON_B_FUSED=0";; esac
-    env $E timeout -k 10 300 python bench.py --steps 20 --warmup 5 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
+    env $E timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
       > "$OUT/ab_${v}_r$r.json" 2> "$OUT/ab_${v}_r$r.err" || { tail "$OUT/ab_${v}_r$r.err"; exit 1; }
     brief "$OUT/ab_${v}_r$r.json" "$v r$r"
   done

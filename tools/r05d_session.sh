@@ -10,14 +10,14 @@ export TMPDIR=/tmp
 step() { echo "[$(date +%T)] $*"; }
 step newton1023
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof_n" -o run --output-format csv -- \
-    python bench.py --size 1023 --steps 2 --warmup 2 --ramp-ms 0 --cpu-sweeps 0 --vcycles 0 --config5 0 --newton-iters 1 > "$OUT/n1023.json" 2> "$OUT/n1023.err" || { tail -20 "$OUT/n1023.err"; exit 1; }
+    python bench.py --full --size 1023 --steps 2 --warmup 2 --ramp-ms 0 --cpu-sweeps 0 --vcycles 0 --config5 0 --newton-iters 1 > "$OUT/n1023.json" 2> "$OUT/n1023.err" || { tail -20 "$OUT/n1023.err"; exit 1; }
 python tools/trace_seq.py "$(find $OUT/prof_n -name '*kernel_trace.csv' -print -quit)" -4 --agg > "$OUT/n1023_seq.txt" && head -32 "$OUT/n1023_seq.txt"
 python -c "import json; d=json.load(open('$OUT/n1023.json')); print('1023^3 newton', d['newton'])"
 step pro-threshold
 for r in 1 2; do
   for v in def p20; do
     if [ $v = p20 ]; then E="GS_NEWTON_PRO_POINTS=1048576"; else E="GS_NONE=1"; fi
-    env $E timeout -k 10 300 python bench.py --steps 4 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
+    env $E timeout -k 10 300 python bench.py --full --steps 4 --warmup 2 --vcycles 0 --cpu-sweeps 0 --config5 0 --newton-iters 2 \
       > "$OUT/pro_${v}_r$r.json" 2> "$OUT/pro_${v}_r$r.err" || { tail "$OUT/pro_${v}_r$r.err"; exit 1; }
     python -c "import json; d=json.load(open('$OUT/pro_${v}_r$r.json')); print('$v r$r', d['newton']['ms_per_iteration'])"
   done

@@ -12,7 +12,7 @@ step bench
 for r in 1 2; do
   for v in g nog; do
     if [ $v = nog ]; then export GS_NO_NEWTON_G=1; else unset GS_NO_NEWTON_G; fi
-    timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-sweeps 0 > "$OUT/bench_${v}_r$r.json" 2> "$OUT/bench_${v}_r$r.err" || { tail -20 "$OUT/bench_${v}_r$r.err"; exit 1; }
+    timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-sweeps 0 > "$OUT/bench_${v}_r$r.json" 2> "$OUT/bench_${v}_r$r.err" || { tail -20 "$OUT/bench_${v}_r$r.err"; exit 1; }
     echo -n "$v r$r "; python tools/bench_brief.py "$OUT/bench_${v}_r$r.json" || true
   done
 done

@@ -16,16 +16,16 @@ GS_FUZZ_N=600 GS_FUZZ_SEED=20261021 timeout -k 10 900 python -u -m pytest tests/
 tail -2 "$OUT/fuzz.log"; fatal $rc
 step bench-driver-flags
 for r in 1 2; do
-  timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_r$r.json" 2> "$OUT/bench_r$r.err" || { tail -20 "$OUT/bench_r$r.err"; exit 1; }
+  timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_r$r.json" 2> "$OUT/bench_r$r.err" || { tail -20 "$OUT/bench_r$r.err"; exit 1; }
   python tools/bench_brief.py "$OUT/bench_r$r.json" || true
 done
 step bench-rocprof-stats
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof_bench" -o run --output-format csv -- \
-    python bench.py --steps 20 --warmup 5 --cpu-sweeps 0 > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err" || { tail -20 "$OUT/prof_bench.err"; exit 1; }
+    python bench.py --full --steps 20 --warmup 5 --cpu-sweeps 0 > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err" || { tail -20 "$OUT/prof_bench.err"; exit 1; }
 python tools/kernel_agg.py "$(find $OUT/prof_bench -name '*kernel_trace.csv' -print -quit)" > "$OUT/prof_bench_agg.txt" && head -24 "$OUT/prof_bench_agg.txt"
 step newton-seq
 timeout -k 10 400 rocprofv3 --kernel-trace -d "$OUT/prof_n" -o run --output-format csv -- \
-    python bench.py --steps 2 --warmup 2 --ramp-ms 0 --cpu-sweeps 0 --vcycles 0 --config5 0 --newton-iters 2 > "$OUT/n512.json" 2> "$OUT/n512.err" || { tail -20 "$OUT/n512.err"; exit 1; }
+    python bench.py --full --steps 2 --warmup 2 --ramp-ms 0 --cpu-sweeps 0 --vcycles 0 --config5 0 --newton-iters 2 > "$OUT/n512.json" 2> "$OUT/n512.err" || { tail -20 "$OUT/n512.err"; exit 1; }
 python tools/trace_seq.py "$(find $OUT/prof_n -name '*kernel_trace.csv' -print -quit)" -4 --agg > "$OUT/n512_seq.txt" && head -40 "$OUT/n512_seq.txt"
 step ranks8
 bash tools/bench_ranks.sh r05m/ranks8 8 256 --vcycles 2 --cpu-sweeps 0 --newton-iters 0 --config5 0 > "$OUT/ranks8.log" 2>&1 || { tail -30 "$OUT/ranks8.log"; exit 1; }

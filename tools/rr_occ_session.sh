@@ -6,7 +6,7 @@ TAG=${1:-rrocc}; shift; VALS=${@:-0 90000}
 OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 for r in 1 2; do
   for v in $VALS; do
-    GS_RR_SHMEM=$v timeout -k 10 200 python bench.py --steps 10 --warmup 5 --vcycles 10 --cpu-sweeps 0 --newton-iters 0 \
+    GS_RR_SHMEM=$v timeout -k 10 200 python bench.py --full --steps 10 --warmup 5 --vcycles 10 --cpu-sweeps 0 --newton-iters 0 \
       --config5 0 > $OUT/b_${v}_r$r.json 2> $OUT/b_${v}_r$r.err || { tail $OUT/b_${v}_r$r.err; exit 1; }
     python -c "import json; d=json.load(open('$OUT/b_${v}_r$r.json')); print('GS_RR_SHMEM=$v r$r vcycle', d['vcycle']['ms'], 'rr2 ms', d['vcycle']['level0_kernels']['residual_restrict']['ms'])"
   done

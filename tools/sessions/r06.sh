@@ -19,16 +19,16 @@ for s in "$@"; do
         tail -3 "$OUT/pytest_$n.log" ;;
     bench)
         step "bench (driver flags)"
-        timeout -k 10 600 python bench.py --steps 20 --warmup 5 > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err" || { tail -20 "$OUT/bench_$n.err"; exit 1; }
+        timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err" || { tail -20 "$OUT/bench_$n.err"; exit 1; }
         cat "$OUT/bench_$n.json" ;;
     benchdef)
         step "bench (defaults)"
-        timeout -k 10 600 python bench.py > "$OUT/benchdef_$n.json" 2> "$OUT/benchdef_$n.err" || { tail -20 "$OUT/benchdef_$n.err"; exit 1; }
+        timeout -k 10 600 python bench.py --full > "$OUT/benchdef_$n.json" 2> "$OUT/benchdef_$n.err" || { tail -20 "$OUT/benchdef_$n.err"; exit 1; }
         cat "$OUT/benchdef_$n.json" ;;
     prof)
         step "rocprof kernel trace of the bench (driver flags, no cpu leg)"
         timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$n" -o run --output-format csv -- \
-            python bench.py --steps 20 --warmup 5 --cpu-sweeps 0 > "$OUT/bench_prof_$n.json" 2> "$OUT/bench_prof_$n.err" || { tail -20 "$OUT/bench_prof_$n.err"; exit 1; } ;;
+            python bench.py --full --steps 20 --warmup 5 --cpu-sweeps 0 > "$OUT/bench_prof_$n.json" 2> "$OUT/bench_prof_$n.err" || { tail -20 "$OUT/bench_prof_$n.err"; exit 1; } ;;
     py:*)
         cmd=${s#py:}
         step "python $cmd"
