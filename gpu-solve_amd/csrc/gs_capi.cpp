@@ -186,6 +186,12 @@ int gs_grid_level_fused(void* grid, int level)
     return G(grid).getLevel(level).fusedPairs ? 1 : 0;
 }
 
+int64_t gs_grid_level_triples(void* grid, int level)
+{
+    if (level < 0 || level >= (int)G(grid).numLevels()) return 0;
+    return G(grid).getLevel(level).triplesRun;
+}
+
 int gs_grid_level(void* grid, int level, gs_level* out)
 {
     if (level < 0 || level >= (int)G(grid).numLevels() || !out) return 1;

@@ -250,6 +250,33 @@ __device__ __forceinline__ void div_hh_n(const Coef& k, double (&s)[N])
     }
 }
 
+// div_hh_n with the operand-range test taken on the minimum and the maximum of the N exponent fields (three-input
+// integer min / max: about two operations per value instead of four): the same predicate — every exponent in
+// 124..1623 — so the same path and the same quotients as div_hh_n
+template <int N>
+__device__ __forceinline__ void div_hh_mm(const Coef& k, double (&s)[N])
+{
+    unsigned lo = 0x7ffu, hi = 0u;
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        const unsigned e = ((unsigned)__double2hiint(s[i]) >> 20) & 0x7ffu;
+        lo = min(lo, e);
+        hi = max(hi, e);
+    }
+    if (k.fastdiv && lo >= 124u && hi <= 1623u) {
+        const double y = hh_recip(k.hh);
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+            const double q = s[i] * y;
+            const double r = __builtin_fma(-k.hh, q, s[i]);
+            s[i] = __builtin_fma(r, y, q);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; i++) s[i] = s[i] / k.hh;
+    }
+}
+
 // one row's two points: batched, except in GS_NEWTON mode whose kernels run at the VGPR limit (the batch
 // keeps both sums live across the branch). GS_NEWTON_B's pairs have the room since r05: batched, NEWTON_B pair
 // 0.840-0.853 vs 0.872-0.885 ms, prolongation pair 0.924-0.930 vs 0.964-0.975 ms, Newton iteration -0.8 ms (r05r)
@@ -3044,6 +3071,260 @@ constexpr int TBY_RY = 2, TBY_RY_NEWTON = 2, TBY_WX = 4, TB_RY_B = 2, TB_WX_B = 
 constexpr int tby_pfd(int mode) { return mode == GS_LINEAR ? 2 : 1; }
 // column blocks (XH): LINEAR at distance 2 too (247 VGPRs, no spill); GS_TBX_PFD=1 selects distance 1 (A/B)
 bool tbx_pfd2() { return kKnobs.tbxPfd2; }
+
+// The fused triple ("tb3y"): three LINEAR sweeps per pass in k_tb2y's whole-row tile (4 x-waves x 2 mirrored y-waves
+// x TBY_RY rows, one 8-wave block per CU, XCD-aware tile order, z-chunks of tb2_plan). At plane step z a block
+// evaluates sweep 1 at plane z, sweep 2 at plane z-1 and sweep 3 at plane z-2 and stores sweep 3, so a sequence of K
+// sweeps takes K/3 passes over memory instead of K/2. Local rows as in k_tb2y (wave 0: j -> y0-1+j, wave 1 the
+// mirror image y0+2RY-j): own rows j = 1..RY, row RY+1 received from the other y-wave through `yrow` (v(z),
+// sweep-1(z-1), sweep-2(z-2)), rows <= 0 recomputed halo. v is loaded on rows -2..RY (row -2 at plane z only), f on
+// rows -1..RY; sweep 1 is evaluated on rows -1..RY, sweep 2 on rows 0..RY, sweep 3 on rows 1..RY: 9 row evaluations
+// per y-wave and step for 2 output rows. One plane step of prefetch (two operand slots), loads grouped by field,
+// one LDS-only barrier per step, the x-edge columns of every stage through `edge` into SGPRs.
+// State a lane only re-reads itself one or two steps later lives in LDS, not in registers (k_tb2y's wprev_l / fprev_l
+// pattern, no barrier): f of planes z-1 / z-2 for sweeps 2 / 3 and the previous-plane rows of sweeps 1 / 2. With that
+// state in registers, or with the edge values in VGPRs as the LINEAR pair keeps them, every instance spills
+// (DESIGN.md §4.1).
+// A chunk recomputes three prologue steps (z = zb-2 .. zb), whose stage values are formed from whatever the
+// zero-initialised state gives and are never consumed by a stored value. Boundary rows, columns and planes keep the
+// input value at every stage; plane addresses are clamped to 0..nz+1. Every point goes through the expressions of the
+// one-sweep kernels in the same operand order, so the output is bit-identical to three gs_jacobi_sweep calls.
+// Whole non-distributed levels only (no ghost-plane sides), a real input iterate, no prolongation, no norm partials.
+// DB: the stencil sums of several rows are divided by h^2 in ONE batch (div_hh_mm over two rows of sweep 1, every row
+// of sweeps 2 and 3: four range branches per step instead of nine, and the rows' dependent chains interleave); else
+// row by row. Each quotient is the same value either way. The unit-stencil instances are batched (252 VGPRs), the
+// general-stencil instance is not (242; batched it spills).
+template <bool UN, bool FX, bool DB>
+__global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double* __restrict__ v,
+                                                           const double* __restrict__ f, double* __restrict__ out,
+                                                           int nx, int ny, int nz, int64_t ldy, int64_t ldz, int ZC)
+{
+    constexpr int MODE = GS_LINEAR, RY = TBY_RY, WXMAX = TBY_WX;
+    static_assert(RY == 2, "k_tb3y: two rows per y-wave (the boundary tests below name the rows)");
+    constexpr int N0 = RY + 2;       // v, f, sweep-1 rows j = -1..RY at index j+1
+    constexpr int N1 = RY + 1;       // sweep-2 rows j = 0..RY at index j
+    constexpr int NE = N0 + N1 + RY; // x-edge values per wave side: v rows -1..RY, sweep-1 rows 0..RY, sweep-2 rows 1..RY
+    constexpr int B1 = DB ? 2 : 1, B2 = DB ? N1 : 1, B3 = DB ? RY : 1; // rows per division batch of sweeps 1, 2, 3
+    // x-edges: [parity][y-wave][1 + x-wave][side][value]; x-wave slots 0 and WX+1 are the zero x-boundary columns
+    __shared__ double edge[2][2][WXMAX + 2][2][NE];
+    // y-edge rows: [parity][y-wave][x-wave][v | sweep-1 | sweep-2][lane]
+    __shared__ double2 yrow[2][2][WXMAX][3][WAVE];
+    // per-lane state, [row][wave][lane]: f at planes z-1 (rows 0..RY) and z-2 (rows 1..RY), sweep 1 at plane z-2
+    // (rows 0..RY), sweep 2 at plane z-3 (rows 1..RY)
+    __shared__ double2 f1_l[N1][2 * WXMAX][WAVE];
+    __shared__ double2 f2_l[RY][2 * WXMAX][WAVE];
+    __shared__ double2 s1p_l[N1][2 * WXMAX][WAVE];
+    __shared__ double2 s2p_l[RY][2 * WXMAX][WAVE];
+    const int lane = threadIdx.x;
+    const int wy = __builtin_amdgcn_readfirstlane(threadIdx.z);
+    const int WX = blockDim.y;
+    const int wx = __builtin_amdgcn_readfirstlane(threadIdx.y);
+    const int wid = wx + WXMAX * wy;
+    const int tid = threadIdx.x + WAVE * (threadIdx.y + WX * threadIdx.z);
+    for (int i = tid; i < 2 * 2 * (WXMAX + 2) * 2 * NE; i += WAVE * WX * 2) (&edge[0][0][0][0][0])[i] = 0.0;
+    __syncthreads();
+    const int64_t tile = xcd_tile(blockIdx.x + (int64_t)gridDim.x * blockIdx.y, (int64_t)gridDim.x * gridDim.y);
+    const int x = 1 + wx * (2 * WAVE) + 2 * lane;
+    const int xl = min(x, nx + 1);
+    const bool bx0 = !FX && x > nx, bx1 = !FX && x + 1 > nx;
+    const bool okx0 = FX || x <= nx, okx1 = FX || x + 1 <= nx;
+    const int y0 = 1 + (int)(tile % gridDim.x) * (2 * RY);
+    const int zb = 1 + (int)(tile / gridDim.x) * ZC;
+    const int ze = min(zb + ZC - 1, nz);
+    const bool mir = wy != 0;
+    auto yof = [&](int j) { return mir ? y0 + 2 * RY - j : y0 - 1 + j; };
+
+    int64_t roff[RY + 3]; // local rows j = -2..RY at index j+2
+    bool rowc[RY + 3];
+#pragma unroll
+    for (int j = -2; j <= RY; j++) {
+        const int y = yof(j);
+        roff[j + 2] = (int64_t)min(max(y, 0), ny + 1) * ldy;
+        rowc[j + 2] = y >= 1 && y <= ny;
+    }
+    const bool in1 = rowc[1] && rowc[2] && rowc[3] && rowc[4]; // every sweep-1 / sweep-2 row is an interior row
+    const bool in2 = rowc[2] && rowc[3] && rowc[4];
+    auto planeok = [&](int z) { return z >= 1 && z <= nz; };
+    auto cz = [&](int z) { return min(max(z, 0), nz + 1); }; // planes below 0 / above nz+1 are never dereferenced
+    auto at = [&](const double* base, int j, int z) { return base + xl + roff[j + 2] + (int64_t)z * ldz; };
+
+    double2 Vp[N0], Vc[N0], VL[2][N0], FL[2][N0], HL[2]; // v(z-1), v(z); per slot: v(z+1), f(z), v(z) at row -2
+    double2 S1c[N0], S2c[N1];                            // sweep 1 at plane z-1, sweep 2 at plane z-2
+#pragma unroll
+    for (int i = 0; i < N0; i++) S1c[i] = make_double2(0.0, 0.0);
+#pragma unroll
+    for (int i = 0; i < N1; i++) {
+        S2c[i] = make_double2(0.0, 0.0);
+        f1_l[i][wid][lane] = make_double2(0.0, 0.0);
+        s1p_l[i][wid][lane] = make_double2(0.0, 0.0);
+    }
+#pragma unroll
+    for (int i = 0; i < RY; i++) {
+        f2_l[i][wid][lane] = make_double2(0.0, 0.0);
+        s2p_l[i][wid][lane] = make_double2(0.0, 0.0);
+    }
+    // a step's loads grouped by field, rows ascending (as the LINEAR plain pair, GRP)
+    auto load_slot = [&](const int s, const int z, const int zv) {
+        HL[s] = ld2(at(v, -2, z));
+#pragma unroll
+        for (int i = 0; i < N0; i++) VL[s][i] = ld2(at(v, i - 1, zv));
+#pragma unroll
+        for (int i = 0; i < N0; i++) FL[s][i] = ld2(at(f, i - 1, z));
+    };
+#pragma unroll
+    for (int i = 0; i < N0; i++) {
+        Vp[i] = ld2(at(v, i - 1, cz(zb - 3)));
+        Vc[i] = ld2(at(v, i - 1, cz(zb - 2)));
+    }
+    load_slot(1, cz(zb - 2), cz(zb - 1));
+    for (int z0 = zb - 2; z0 <= ze + 2; z0 += 2) {
+#pragma unroll
+        for (int ph = 0; ph < 2; ph++) {
+            const int z = z0 + ph; // (a step past ze+2 loads clamped planes and stores nothing)
+            const int cs = ph ^ 1; // slot holding this step's operands
+            load_slot(ph, cz(z + 1), cz(z + 2));
+            // ---- publish: x-edge columns of the three stages and the y-edge rows
+            if (lane == 0) {
+#pragma unroll
+                for (int i = 0; i < N0; i++) edge[ph][wy][wx + 1][0][i] = Vc[i].x;
+#pragma unroll
+                for (int i = 0; i < N1; i++) edge[ph][wy][wx + 1][0][N0 + i] = S1c[i + 1].x;
+#pragma unroll
+                for (int i = 0; i < RY; i++) edge[ph][wy][wx + 1][0][N0 + N1 + i] = S2c[i + 1].x;
+            }
+            if (lane == WAVE - 1) {
+#pragma unroll
+                for (int i = 0; i < N0; i++) edge[ph][wy][wx + 1][1][i] = Vc[i].y;
+#pragma unroll
+                for (int i = 0; i < N1; i++) edge[ph][wy][wx + 1][1][N0 + i] = S1c[i + 1].y;
+#pragma unroll
+                for (int i = 0; i < RY; i++) edge[ph][wy][wx + 1][1][N0 + N1 + i] = S2c[i + 1].y;
+            }
+            yrow[ph][wy][wx][0][lane] = Vc[N0 - 1];
+            yrow[ph][wy][wx][1][lane] = S1c[N0 - 1];
+            yrow[ph][wy][wx][2][lane] = S2c[N1 - 1];
+            // LDS-only barrier: the outstanding prefetch stays in flight across it
+            GS_LDS_BARRIER();
+            double CL[NE], CR[NE];
+#pragma unroll
+            for (int i = 0; i < NE; i++) { // wave-uniform: kept in SGPRs
+                CL[i] = uniform_d(edge[ph][wy][wx][1][i]);
+                CR[i] = uniform_d(edge[ph][wy][wx + 2][0][i]);
+            }
+            const double2 vY = yrow[ph][wy ^ 1][wx][0][lane];  // v(z) at local row RY+1
+            const double2 s1Y = yrow[ph][wy ^ 1][wx][1][lane]; // sweep-1(z-1) at local row RY+1
+            const double2 s2Y = yrow[ph][wy ^ 1][wx][2][lane]; // sweep-2(z-2) at local row RY+1
+
+            // one row of one stage in two halves around the division: the stencil sums of the lane's two points from
+            // the row's centre, its y- and z-neighbour rows and the x-edge values of the wave; then the new values
+            auto row_sums = [&](auto mirc, const double2 c, const double2 lm, const double2 lp, const double2 zm,
+                                const double2 zp, const double el, const double er, double& q0, double& q1) {
+                constexpr bool M = decltype(mirc)::get();
+                const double2 ym = M ? lp : lm, yp = M ? lm : lp;
+                const double xm0 = lane_from_left<true>(c.y, el);
+                const double xp1 = lane_from_right<true>(c.x, er);
+                q0 = stencil_sum<UN>(k, c.x, c.y, xm0, yp.x, ym.x, zp.x, zm.x);
+                q1 = stencil_sum<UN>(k, c.y, xp1, c.x, yp.y, ym.y, zp.y, zm.y);
+            };
+            auto row_finish = [&](const double2 c, const double q0, const double q1, const double2 fv) {
+                const double a0 = op_finish<MODE>(k, q0, c.x, 0.0);
+                const double a1 = op_finish<MODE>(k, q1, c.y, 0.0);
+                return make_double2(jacobi_update<MODE>(k, c.x, fv.x - a0, 0.0),
+                                    jacobi_update<MODE>(k, c.y, fv.y - a1, 0.0));
+            };
+            auto kept = [&](const bool keep, const double2 c, const double2 n) {
+                return make_double2((keep || bx0) ? c.x : n.x, (keep || bx1) ? c.y : n.y);
+            };
+            // ---- the three sweeps; wave 1 (mirrored rows) runs its own copy of the code. The keep selects run only
+            // where some row, column or the plane is a boundary (a wave-uniform branch)
+            double2 S1n[N0], S2n[N1], F1[N1]; // F1: f at plane z-1 as sweep 2 read it (-> f2_l)
+            const bool pz0 = planeok(z), pz1 = planeok(z - 1);
+            auto sweeps = [&](auto mirc) {
+                // sweep 1 at plane z, local rows -1..RY
+                static_assert(N0 % B1 == 0 && N1 % B2 == 0 && RY % B3 == 0, "whole division batches");
+#pragma unroll
+                for (int b = 0; b < N0; b += B1) {
+                    double q[2 * B1];
+#pragma unroll
+                    for (int i = b; i < b + B1; i++)
+                        row_sums(mirc, Vc[i], i == 0 ? HL[cs] : Vc[i - 1], i == N0 - 1 ? vY : Vc[i + 1], Vp[i], VL[cs][i],
+                                 CL[i], CR[i], q[2 * (i - b)], q[2 * (i - b) + 1]);
+                    div_hh_mm(k, q);
+#pragma unroll
+                    for (int i = b; i < b + B1; i++) S1n[i] = row_finish(Vc[i], q[2 * (i - b)], q[2 * (i - b) + 1], FL[cs][i]);
+                }
+                if (!FX || !pz0 || !in1) {
+#pragma unroll
+                    for (int i = 0; i < N0; i++) S1n[i] = kept(!pz0 || !rowc[i + 1], Vc[i], S1n[i]);
+                }
+                // sweep 2 at plane z-1, local rows 0..RY
+#pragma unroll
+                for (int b = 0; b < N1; b += B2) {
+                    double q[2 * B2];
+#pragma unroll
+                    for (int i = b; i < b + B2; i++) {
+                        F1[i] = f1_l[i][wid][lane];
+                        row_sums(mirc, S1c[i + 1], S1c[i], i == N1 - 1 ? s1Y : S1c[i + 2], s1p_l[i][wid][lane], S1n[i + 1],
+                                 CL[N0 + i], CR[N0 + i], q[2 * (i - b)], q[2 * (i - b) + 1]);
+                    }
+                    div_hh_mm(k, q);
+#pragma unroll
+                    for (int i = b; i < b + B2; i++)
+                        S2n[i] = row_finish(S1c[i + 1], q[2 * (i - b)], q[2 * (i - b) + 1], F1[i]);
+                }
+                if (!FX || !pz1 || !in2) {
+#pragma unroll
+                    for (int i = 0; i < N1; i++) S2n[i] = kept(!pz1 || !rowc[i + 2], S1c[i + 1], S2n[i]);
+                }
+                // sweep 3 at plane z-2, own rows 1..RY
+                if (z - 2 >= zb && z - 2 <= ze) {
+                    const int64_t zo = (int64_t)(z - 2) * ldz;
+#pragma unroll
+                    for (int b = 1; b <= RY; b += B3) {
+                        double q[2 * B3];
+                        double2 fv[B3];
+#pragma unroll
+                        for (int j = b; j < b + B3; j++) {
+                            fv[j - b] = f2_l[j - 1][wid][lane];
+                            row_sums(mirc, S2c[j], S2c[j - 1], j == RY ? s2Y : S2c[j + 1], s2p_l[j - 1][wid][lane], S2n[j],
+                                     CL[N0 + N1 + j - 1], CR[N0 + N1 + j - 1], q[2 * (j - b)], q[2 * (j - b) + 1]);
+                        }
+                        div_hh_mm(k, q);
+#pragma unroll
+                        for (int j = b; j < b + B3; j++) {
+                            const double2 o = row_finish(S2c[j], q[2 * (j - b)], q[2 * (j - b) + 1], fv[j - b]);
+                            if (yof(j) <= ny) {
+                                double* qo = out + x + roff[j + 2] + zo;
+                                if (okx1) st2s<true>(qo, o.x, o.y);
+                                else if (okx0) *qo = o.x;
+                            }
+                        }
+                    }
+                }
+            };
+            if (mir) sweeps(BoolC<true>{});
+            else sweeps(BoolC<false>{});
+            // ---- rotate (each lane's LDS rows were read above by this lane alone) ----
+#pragma unroll
+            for (int j = 1; j <= RY; j++) {
+                s2p_l[j - 1][wid][lane] = S2c[j];
+                f2_l[j - 1][wid][lane] = F1[j];
+            }
+#pragma unroll
+            for (int i = 0; i < N1; i++) {
+                S2c[i] = S2n[i];
+                s1p_l[i][wid][lane] = S1c[i + 1];
+                f1_l[i][wid][lane] = FL[cs][i + 1];
+            }
+#pragma unroll
+            for (int i = 0; i < N0; i++) {
+                S1c[i] = S1n[i];
+                Vp[i] = Vc[i];
+                Vc[i] = VL[cs][i];
+            }
+        }
+    }
+}
 
 // Column blocks (k_tb2y XH) for rows of more than 512 points in LINEAR / NONLINEAR mode: 1024-point rows
 // (BASELINE config #5) were k_tb2's one-y-wave shape before; GS_PAIR_XH=0 restores that (A/B).

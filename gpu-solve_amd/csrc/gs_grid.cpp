@@ -196,6 +196,8 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
         if (const char* e = std::getenv("GS_NEWTON_PRO_POINTS")) sw.newtonProPoints = std::strtoll(e, nullptr, 10);
         if (const char* e = std::getenv("GS_TILE_POINTS")) sw.tilePoints = std::strtoll(e, nullptr, 10);
         if (const char* e = std::getenv("GS_HALO_ORDER")) sw.haloOrder = std::atoi(e);
+        sw.sweep3 = !on("GS_NO_SWEEP3");
+        if (const char* e = std::getenv("GS_SWEEP3_MIN_POINTS")) sw.sweep3MinPoints = std::strtoll(e, nullptr, 10);
     }
     std::vector<int64_t> nzs, pts;
     for (int l = 0; l < nlev; l++) {
@@ -249,6 +251,8 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
         thin.nz = L.minPlanes;
         L.fusedPairs = sw.fusedSweeps && gs_jacobi_sweep2_supported_mode(&stencilAbi, &thin, (int)mode) == 2 &&
                        (!L.distributed || L.minPlanes >= 2);
+        L.fusedTriples = sw.sweep3 && sw.fusedSweeps && mode == LINEAR && !L.distributed && pts[l] >= sw.sweep3MinPoints &&
+                         gs_jacobi_sweep3_supported(&stencilAbi, &L.geom) == 2;
         L.tiled = !L.distributed && pts[l] <= sw.tilePoints &&
                   gs_tiled_supported(&stencilAbi, &L.geom, (int)mode) != 0;
     }
@@ -536,6 +540,13 @@ int64_t pairPlanes(HipGridData& g, HipGridData::LevelData& L, int64_t z1, int64_
     return partials ? gs_jacobi_sweep2_num_partials(&g.stencilAbi, &sub, (int)g.mode) : 0;
 }
 
+// three fused LINEAR sweeps over a whole non-distributed level (gs_jacobi_sweep3): reads L.v, writes L.vAlt
+void tripleLevel(HipGridData& g, HipGridData::LevelData& L, hipStream_t s)
+{
+    check(gs_jacobi_sweep3(&g.stencilAbi, &L.geom, g.omega, g.gamma, L.v.data(), L.vAlt.data(), L.f.data(), s),
+          "gs_jacobi_sweep3");
+}
+
 // The first post-smoothing pair of v^h + P v^2h (gs_jacobi_sweep2_prolong) on planes z1..z2 of F
 // into F.vAlt. Every plane range starts on an odd plane (the kernel's parities are global ones) and
 // ends two planes below the level's top or on it: the planes past an internal range end are
@@ -816,6 +827,16 @@ void HipSolver::jacobi(HipGridData& grid, std::size_t l, std::size_t sweeps)
     const int depth = grid.vDepth(L);
     int step = 0; // overlapped steps issued in this call
     while (sweeps > 0) {
+        // a fused triple where the level takes them and the rest of the sequence still splits into triples and
+        // pairs (3: T, 4: P P, 5: T P, 6: T T, 7: T P P, ...): never on a Z-slab, in the schedule trace or on
+        // the zero iterate, which keep the pair schedule
+        if (L.fusedTriples && !dist && !grid.trace && !L.vZero && (sweeps == 3 || sweeps >= 5)) {
+            tripleLevel(grid, L, s);
+            L.triplesRun++;
+            L.v.swap(L.vAlt);
+            sweeps -= 3;
+            continue;
+        }
         const bool pair = L.fusedPairs && sweeps >= 2;
         const int64_t b = pair ? 2 : depth; // outermost planes whose ghost copies the neighbours need
         auto run = [&](int64_t z1, int64_t z2, hipStream_t st) {

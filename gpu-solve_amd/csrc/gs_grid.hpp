@@ -110,6 +110,8 @@ public:
         gs_level geom{};     // kernel-side geometry of the stored array (slab or full level)
         bool distributed = false;
         bool fusedPairs = false; // smoothing runs as fused sweep pairs (gs_jacobi_sweep2)
+        bool fusedTriples = false; // long LINEAR sweep sequences run as fused triples (gs_jacobi_sweep3)
+        int64_t triplesRun = 0;    // fused triples launched on this level so far (gs_grid_level_triples)
         bool vZero = false;      // v is identically zero but not stored: the next sweep reads no v
         bool tiled = false;      // small LINEAR level: down- and up-leg steps as one tiled launch each
         int64_t lo = 1, hi = 0; // this rank's owned global planes (== 1..nz when not distributed)
@@ -162,6 +164,9 @@ public:
         int64_t newtonProPoints = (int64_t)1 << 21; // GS_NEWTON_PRO_POINTS: NEWTON levels take the fused
                                                      // prolongation pair from this many points per rank (r06: 2^21,
                                                      // 128^3 too, was 2^24)
+        bool sweep3 = true; // GS_NO_SWEEP3: no fused triples (gs_jacobi_sweep3) in LINEAR sweep sequences
+        int64_t sweep3MinPoints = (int64_t)1 << 26; // GS_SWEEP3_MIN_POINTS: levels take triples from this many points
+                                                     // (2^26: the levels whose pair runs one round of blocks)
         // GS_HALO_ORDER: in a pipelined Z-slab sweep sequence, interior k goes before boundary k when
         // exchange k-1 has not settled on the host yet (0, adaptive), always (1), or never (2: boundary first)
         int haloOrder = 0;

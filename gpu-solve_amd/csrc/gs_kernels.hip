@@ -186,6 +186,37 @@ int gs_jacobi_sweep2_norm(const gs_stencil* S, const gs_level* L, int mode, doub
     return launch_status();
 }
 
+// The fused triple (k_tb3y): LINEAR, whole rows of <= 512 points, whole levels (z0 = 0), the pair's plan
+int gs_jacobi_sweep3_supported(const gs_stencil* S, const gs_level* L)
+{
+    int zc;
+    dim3 g, b;
+    bool y2 = false, xh = false;
+    if (!S || bad_level(L) || !valid_stencil(S) || L->z0 != 0) return 0;
+    const int q = tb2_plan(S, L, &zc, &g, &b, &y2, GS_LINEAR, &xh);
+    return y2 ? q : 0;
+}
+
+int gs_jacobi_sweep3(const gs_stencil* S, const gs_level* L, double omega, double gamma, const double* v_in,
+                     double* v_out, const double* f, hipStream_t st)
+{
+    int zc;
+    dim3 g, b;
+    bool y2 = false, xh = false;
+    if (!S || bad_level(L) || !valid_stencil(S) || L->z0 != 0 || !v_in || !v_out || !f || v_in == v_out ||
+        !tb2_plan(S, L, &zc, &g, &b, &y2, GS_LINEAR, &xh) || !y2)
+        return GS_EINVAL;
+    const Coef k = make_coef(S, L, omega, gamma);
+    const int nx = (int)L->nx, ny = (int)L->ny, nz = (int)L->nz;
+#define GS_TB3(U, X) hipLaunchKernelGGL((k_tb3y<U, X, U>), g, b, 0, st, k, v_in, f, v_out, nx, ny, nz, L->ldy, L->ldz, zc)
+    // FX: rows of whole 128-point waves, as the pair's (GS_PAIR_FX=0: the general instance)
+    if (k.unit && kKnobs.pairFx && nx % (2 * WAVE) == 0) GS_TB3(true, true);
+    else if (k.unit) GS_TB3(true, false);
+    else GS_TB3(false, false);
+#undef GS_TB3
+    return launch_status();
+}
+
 int gs_jacobi_sweep2_prolong_supported(const gs_stencil* S, const gs_level* L, int mode)
 {
     int zc;
@@ -766,7 +797,8 @@ const char* gs_strerror(int code)
 
 const char* gs_build_info(void)
 {
-    return "gpusolve_hip v13: pairs k_tb2y(4x2 waves, 2 rows/wave, one round of z-chunks on large levels, LINEAR 2-step prefetch; +prolong; "
+    return "gpusolve_hip v14: LINEAR triples k_tb3y(the pair's whole-row tile, three sweeps per pass, one-step prefetch, "
+           "per-lane f / previous-plane rows in LDS), pairs k_tb2y(4x2 waves, 2 rows/wave, one round of z-chunks on large levels, LINEAR 2-step prefetch; +prolong; "
            "512-point column blocks for longer rows in every mode; from 64^3 levels; zero-iterate chunks fitted to "
            "resident rounds; zero iterates q = +0; whole-wave rows without range selects (FX); LINEAR loads grouped by "
            "field; x-edge values in VGPRs for LINEAR and the NEWTON_B whole-row plain pair), sweeps k_rb(ry2 w4 zc<=32 "

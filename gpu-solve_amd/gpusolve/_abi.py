@@ -59,6 +59,9 @@ KERNEL_API = {
                                         C.c_int, C.c_void_p, C.c_void_p]),
     "gs_jacobi_sweep2_num_partials": (i64, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int]),
     "gs_jacobi_sweep2_kernel": (C.c_char_p, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int]),
+    "gs_jacobi_sweep3_supported": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level)]),
+    "gs_jacobi_sweep3": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_double, C.c_double,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gs_jacobi_sweep2_prolong_supported": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int]),
     "gs_jacobi_sweep2_prolong": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int, C.c_double, C.c_double,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(gs_level), C.c_void_p,
@@ -129,6 +132,7 @@ DRIVER_API = {
     "gs_grid_residual_norm": (C.c_int, [C.c_void_p, C.c_int, dptr]),
     "gs_grid_num_levels": (C.c_int, [C.c_void_p]),
     "gs_grid_level_fused": (C.c_int, [C.c_void_p, C.c_int]),
+    "gs_grid_level_triples": (i64, [C.c_void_p, C.c_int]),
     "gs_grid_level": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(gs_level)]),
     "gs_grid_field": (C.c_void_p, [C.c_void_p, C.c_int, C.c_int]),
     "gs_grid_stream": (C.c_void_p, [C.c_void_p]),

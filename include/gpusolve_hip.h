@@ -124,6 +124,14 @@ int gs_jacobi_sweep2_norm(const gs_stencil* S, const gs_level* L, int mode, doub
                           const double* v_in, double* v_out, const double* f, const double* w, int zlo, int zhi,
                           double* partials, hipStream_t stream);
 int64_t gs_jacobi_sweep2_num_partials(const gs_stencil* S, const gs_level* L, int mode);
+/* Three fused LINEAR sweeps, v_out = S(S(S(v_in))), reading v_in / f once (bit-identical to three gs_jacobi_sweep
+ * calls in GS_LINEAR mode). Whole levels only (L->z0 == 0, no ghost-plane sides), rows of at most 512 points, a
+ * real input iterate. gs_jacobi_sweep3_supported: 0 impossible (then gs_jacobi_sweep3 returns GS_EINVAL), 1
+ * possible, 2 possible and large enough to fill the GPU, as gs_jacobi_sweep2_supported. The x-boundary columns
+ * of v_in must be zero, as for gs_jacobi_sweep2. */
+int gs_jacobi_sweep3_supported(const gs_stencil* S, const gs_level* L);
+int gs_jacobi_sweep3(const gs_stencil* S, const gs_level* L, double omega, double gamma, const double* v_in,
+                     double* v_out, const double* f, hipStream_t stream);
 /* Prolongation + correction fused into the first post-smoothing pair: v_out = S(S(v_in + P(c))) with
  * c = coarse_v (LINEAR) or coarse_v - coarse_sub (NONLINEAR, FAS: CpuSolver.cpp:121-125), P the
  * trilinear interpolation of gs_prolong_add; bit-identical to gs_prolong_add followed by
