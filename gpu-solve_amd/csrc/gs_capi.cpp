@@ -165,6 +165,24 @@ int gs_grid_vcycle(void* grid, double* residual)
     });
 }
 
+int gs_grid_vcycle_level(void* grid, int level)
+{
+    return guarded([&] {
+        if (level < 0) throw gs::Error("vcycleFrom: no such level");
+        gs::HipSolver::vcycleFrom(G(grid), (std::size_t)level);
+    });
+}
+
+int gs_grid_fmg(void* grid, int cycles_per_level, double* residual)
+{
+    return guarded([&] {
+        const double r = gs::HipSolver::fmg(G(grid), cycles_per_level);
+        if (residual) *residual = r;
+    });
+}
+
+int gs_grid_fmg_start_level(void* grid) { return (int)gs::HipSolver::fmgStartLevel(G(grid)); }
+
 int gs_grid_jacobi(void* grid, int level, int sweeps)
 {
     return guarded([&] { gs::HipSolver::jacobi(G(grid), (std::size_t)level, (std::size_t)sweeps); });

@@ -136,11 +136,13 @@ bool valid_stencil(const gs_stencil* S)
 //   GS_SPEC_CACHED=1     pairs with norm partials store through the caches, not non-temporally (A/B)
 //   GS_RR_NG=2           k_rr2 with two groups of coarse rows per block (default 1: measured faster, r05b)
 //   GS_PAIR_FX=0         LINEAR plain pairs always through the instance with per-lane range selects (A/B, r06)
+//   GS_FMG_NT=0|1        gs_fmg_prolong's fine stores never / always non-temporal (default: from 2^25 fine points) (A/B)
 struct Knobs {
     bool unitStencil, tbxPfd2, pairXh, fitRounds, bigChunks, oneRound, rrLds, zeroQ, newtonXh, specCached;
     int xhSwizzle, midZc, rrZc, rrZcBig, oneRoundMid, rbZc;
     int slabZc, pairZc, rrNr, rrNtu, rrReverse, rrNg, rrDma;
     bool pairFx;
+    int fmgNt;
     int64_t pairMinBlocks;
     static int num(const char* name, int dflt)
     {
@@ -155,7 +157,7 @@ struct Knobs {
           newtonXh(num("GS_NEWTON_XH", 1) != 0), specCached(num("GS_SPEC_CACHED", 0) != 0),
           xhSwizzle(num("GS_XH_SWIZZLE", 1)), midZc(num("GS_MID_ZC", 0)), rrZc(num("GS_RR_ZC", 0)), rrZcBig(num("GS_RR_ZC_BIG", 0)), oneRoundMid(num("GS_PAIR_ONE_ROUND_MID", 0)), rbZc(num("GS_RB_ZC", 0)), slabZc(num("GS_SLAB_ZC", 0)), pairZc(num("GS_PAIR_ZC", 0)),
           rrNr(num("GS_RR_NR", 0)), rrNtu(num("GS_RR_NTU", 2)), rrReverse(num("GS_RR_REVERSE", 1)), rrNg(num("GS_RR_NG", 0)), rrDma(num("GS_RR_DMA", 0)),
-          pairFx(num("GS_PAIR_FX", 1) != 0),
+          pairFx(num("GS_PAIR_FX", 1) != 0), fmgNt(num("GS_FMG_NT", -1)),
           pairMinBlocks(num("GS_PAIR_MIN_BLOCKS", 128))
     {
     }
@@ -2025,6 +2027,193 @@ __global__ __launch_bounds__(256) void k_axpy(double* __restrict__ y, const doub
         if (a == 1.0) y[i] = y[i] + x[i];
         else if (a == -1.0) y[i] = y[i] - x[i];
         else y[i] = y[i] + a * x[i];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Full multigrid's prolongation of a SOLUTION (gs_fmg_prolong; not a reference operator): tricubic, separable,
+// evaluated x, then y, then z, on aligned levels (fine n = 2 coarse n + 1 per axis, so padded fine index 2i is coarse
+// index i; the boundary ring takes part as data). Per axis, "cell" i = 0..c produces the odd fine index 2i+1 from
+// four consecutive coarse values (three when c = 1) and, for i < c, the even index 2i+2 by injection:
+//   1 <= i <= c-1   (((-w[i-1] + 9 w[i]) + 9 w[i+1]) - w[i+2]) / 16
+//   i = 0           (((5 w[0] + 15 w[1]) - 5 w[2]) + w[3]) / 16           i = c: the mirror image from the top end
+//   c = 1           ((3 w[0] + 6 w[1]) - w[2]) / 8                          and its mirror
+// fmg_axis gives the first index q of the cell's window, which formula it takes (kind 0 / 1 / 2), whether the
+// operands run downwards from the window's top (rev) and where the injected value sits in the window (ev: 1 or 2).
+__device__ __forceinline__ void fmg_axis(int i, int c, int& q, int& kind, bool& rev, int& ev)
+{
+    if (c == 1) {
+        q = 0;
+        kind = 2;
+        rev = i != 0;
+    } else if (i <= 0) {
+        q = 0;
+        kind = 1;
+        rev = false;
+    } else if (i >= c) {
+        q = c - 2;
+        kind = 1;
+        rev = true;
+    } else {
+        q = i - 1;
+        kind = 0;
+        rev = false;
+    }
+    ev = i + 1 - q;
+}
+
+__device__ __forceinline__ double fmg_interp(int kind, bool rev, double w0, double w1, double w2, double w3)
+{
+    if (kind == 0) return (((-w0 + 9.0 * w1) + 9.0 * w2) - w3) / 16.0;
+    if (kind == 1) {
+        const double a = rev ? w3 : w0, b = rev ? w2 : w1, c = rev ? w1 : w2, d = rev ? w0 : w3;
+        return (((5.0 * a + 15.0 * b) - 5.0 * c) + d) / 16.0;
+    }
+    const double a = rev ? w2 : w0, c = rev ? w0 : w2; // three values: w3 is not read
+    return ((3.0 * a + 6.0 * w1) - c) / 8.0;
+}
+
+// One block: FP_TX x-cells (a wave: one 16-byte store of the fine pair 2i+1, 2i+2 per lane, 1 KiB per row) by FP_TY
+// y-cells (one wave each), marching a chunk of z-cells. Per coarse plane the block stages the tile's rows and
+// columns with their -1 / +2 halo in LDS (two buffers, one barrier per plane: plane p+1, loaded a step earlier, is
+// written while plane p is computed, and plane p+2's loads are in flight), each thread forms the x- then
+// y-interpolated values of its 2 x 2 fine columns on that plane, and the z pass runs on a sliding window of four such
+// planes in registers. Loads stay inside the padded coarse array: the staged index ranges are clamped to it, and so
+// are the windows.
+constexpr int FP_TX = 64, FP_TY = 4, FP_LW = FP_TX + 4, FP_LR = FP_TY + 3;
+
+template <bool NT>
+__global__ __launch_bounds__(FP_TX* FP_TY) void k_fmg_prolong(const double* __restrict__ c, double* __restrict__ f,
+                                                               int cnx, int cny, int cnz, int64_t cldy, int64_t cldz,
+                                                               int64_t fldy, int64_t fldz, int zc, int al)
+{
+    __shared__ double pl[2][FP_LR][FP_LW];
+    // (the wave's y-cell in an SGPR: its formula and window rows are then chosen by scalar branches)
+    const int lane = threadIdx.x, wy = __builtin_amdgcn_readfirstlane(threadIdx.y), tid = wy * FP_TX + lane;
+    const int i0 = blockIdx.x * FP_TX, j0 = blockIdx.y * FP_TY, k0 = blockIdx.z * zc, k1 = min(k0 + zc, cnz + 1);
+    // staged columns / rows / planes: what the tile's windows cover, inside the padded coarse array
+    const int clo = min(max(i0 - 1, 0), max(cnx - 2, 0)), chi = min(i0 + FP_TX + 1, cnx + 1), ncol = chi - clo + 1;
+    const int rlo = min(max(j0 - 1, 0), max(cny - 2, 0)), rhi = min(j0 + FP_TY + 1, cny + 1), nrow = rhi - rlo + 1;
+    const int pstart = min(max(k0 - 1, 0), max(cnz - 2, 0)), pend = min(k1 + 1, cnz + 1);
+    const int i = i0 + lane, j = j0 + wy;
+    const bool okx = i <= cnx, oky = j <= cny, x2 = i < cnx, y2 = j < cny;
+    int qx, kx, ex, qy, ky, ey;
+    bool rx, ry;
+    fmg_axis(min(i, cnx), cnx, qx, kx, rx, ex);
+    fmg_axis(min(j, cny), cny, qy, ky, ry, ey);
+    const bool xedge_wave = __any(kx != 0) != 0;
+    // window positions in the staged plane (a three-value axis repeats its last index; that operand is not used)
+    int lc[4], lr[4];
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+        lc[m] = min(qx + m, cnx + 1) - clo;
+        lr[m] = min(qy + m, cny + 1) - rlo;
+    }
+    // the (at most two) staged elements this thread loads per plane
+    const int n = nrow * ncol;
+    int64_t goff[2];
+    int loff[2];
+    bool gok[2];
+#pragma unroll
+    for (int m = 0; m < 2; m++) {
+        const int e = tid + m * FP_TX * FP_TY;
+        gok[m] = e < n;
+        const int r = gok[m] ? e / ncol : 0, col = gok[m] ? e - r * ncol : 0;
+        goff[m] = (clo + col) + (int64_t)(rlo + r) * cldy;
+        loff[m] = r * FP_LW + col;
+    }
+    static_assert(FP_LR * (FP_TX + 3) <= 2 * FP_TX * FP_TY, "two staged elements per thread cover a plane");
+    double g[2], gn[2]; // the thread's elements of plane p + 1 (loaded a step ago) and p + 2 (in flight)
+#pragma unroll
+    for (int m = 0; m < 2; m++) g[m] = gok[m] ? c[goff[m] + (int64_t)pstart * cldz] : 0.0;
+#pragma unroll
+    for (int m = 0; m < 2; m++)
+        if (gok[m]) (&pl[0][0][0])[loff[m]] = g[m];
+#pragma unroll
+    for (int m = 0; m < 2; m++) g[m] = gok[m] && pstart < pend ? c[goff[m] + (int64_t)(pstart + 1) * cldz] : 0.0;
+    __syncthreads();
+
+    // fine pairs (x odd, x even) of the thread's two fine rows on the last four coarse planes
+    double2 wo[4], we[4]; // [plane]: row 2j+1, row 2j+2
+#pragma unroll
+    for (int m = 0; m < 4; m++) wo[m] = we[m] = make_double2(0.0, 0.0);
+    double* const frow = f + (2 * i + 1) + (int64_t)(2 * j + 1) * fldy;
+    auto store = [&](int64_t off, double2 v) {
+        double* p = frow + off;
+        if (x2) {
+            if (al) st2s<NT>(p, v.x, v.y);
+            else {
+                p[0] = v.x;
+                p[1] = v.y;
+            }
+        } else {
+            p[0] = v.x;
+        }
+    };
+    // fine planes 2k+1 (kind, rev over the window a..d) and, with ev, 2k+2 (the window's plane ev)
+    auto emit = [&](int k, int kind, bool rev, const double2& ao, const double2& ae, const double2& bo,
+                    const double2& be, const double2& co, const double2& ce, const double2& d_o, const double2& de,
+                    int ev) {
+        if (!(okx && oky)) return;
+        const int64_t z = (int64_t)(2 * k + 1) * fldz;
+        store(z, make_double2(fmg_interp(kind, rev, ao.x, bo.x, co.x, d_o.x), fmg_interp(kind, rev, ao.y, bo.y, co.y, d_o.y)));
+        if (y2)
+            store(z + fldy,
+                  make_double2(fmg_interp(kind, rev, ae.x, be.x, ce.x, de.x), fmg_interp(kind, rev, ae.y, be.y, ce.y, de.y)));
+        if (ev) {
+            store(z + fldz, ev == 1 ? bo : co);
+            if (y2) store(z + fldz + fldy, ev == 1 ? be : ce);
+        }
+    };
+
+    int cur = 0;
+    for (int p = pstart; p <= pend; p++) {
+        const bool more = p < pend;
+#pragma unroll
+        for (int m = 0; m < 2; m++) gn[m] = gok[m] && p + 2 <= pend ? c[goff[m] + (int64_t)(p + 2) * cldz] : 0.0;
+        // x pass on the window's four rows, then the y pass
+        double xo[4], xe[4];
+#pragma unroll
+        for (int m = 0; m < 4; m++) {
+            const double* row = pl[cur][lr[m]];
+            const double a = row[lc[0]], b = row[lc[1]], cc = row[lc[2]], d = row[lc[3]];
+            // every lane takes the interior formula; the waves holding x-cell 0 or cnx redo that one lane
+            double o = fmg_interp(0, false, a, b, cc, d);
+            if (xedge_wave) {
+                if (kx != 0) o = fmg_interp(kx, rx, a, b, cc, d);
+            }
+            xo[m] = o;
+            xe[m] = ex == 1 ? b : cc;
+        }
+#pragma unroll
+        for (int m = 0; m < 3; m++) {
+            wo[m] = wo[m + 1];
+            we[m] = we[m + 1];
+        }
+        wo[3] = make_double2(fmg_interp(ky, ry, xo[0], xo[1], xo[2], xo[3]), fmg_interp(ky, ry, xe[0], xe[1], xe[2], xe[3]));
+        we[3] = make_double2(ey == 1 ? xo[1] : xo[2], ey == 1 ? xe[1] : xe[2]);
+        // the z-cells complete with plane p (wo / we [m] hold plane p - 3 + m)
+        if (cnz == 1) {
+            if (p == 2) {
+                emit(0, 2, false, wo[1], we[1], wo[2], we[2], wo[3], we[3], wo[3], we[3], 1);
+                emit(1, 2, true, wo[1], we[1], wo[2], we[2], wo[3], we[3], wo[3], we[3], 0);
+            }
+        } else {
+            if (p == 3 && k0 == 0) emit(0, 1, false, wo[0], we[0], wo[1], we[1], wo[2], we[2], wo[3], we[3], 1);
+            const int k = p - 2;
+            if (k >= 1 && k <= cnz - 1 && k >= k0 && k < k1)
+                emit(k, 0, false, wo[0], we[0], wo[1], we[1], wo[2], we[2], wo[3], we[3], 2);
+            if (p == cnz + 1 && k1 > cnz) emit(cnz, 1, true, wo[0], we[0], wo[1], we[1], wo[2], we[2], wo[3], we[3], 0);
+        }
+        if (more) {
+#pragma unroll
+            for (int m = 0; m < 2; m++)
+                if (gok[m]) (&pl[cur ^ 1][0][0])[loff[m]] = g[m];
+        }
+        __syncthreads();
+        cur ^= 1;
+        g[0] = gn[0];
+        g[1] = gn[1];
     }
 }
 

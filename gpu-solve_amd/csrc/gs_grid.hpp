@@ -170,6 +170,9 @@ public:
         // GS_HALO_ORDER: in a pipelined Z-slab sweep sequence, interior k goes before boundary k when
         // exchange k-1 has not settled on the host yet (0, adaptive), always (1), or never (2: boundary first)
         int haloOrder = 0;
+        // GS_FMG=k (default 0, off): HipSolver::solve starts with a full-multigrid pass of k V-cycles per level
+        // (HipSolver::fmg) before its first V-cycle — the one switch that changes the iterate
+        int fmg = 0;
     } sw;
     // levels coarseFrom .. numLevels()-1 run as ONE gs_coarse_cycle launch in every V-cycle
     // (numLevels(): none); set from GS_COARSE_POINTS at construction
@@ -275,6 +278,24 @@ public:
     // only if `wait` (else the caller collects it with grid.readNormEnd()).
     static void cycleDown(HipGridData& grid, int* pending);
     static double cycleUp0(HipGridData& grid, int* pending, bool wait);
+    // cycleDown rooted at level `from` (cycleDown is from = 0): the down-legs from..., the coarse end — the one
+    // gs_coarse_cycle launch from max(from, coarseFrom) on, or the coarsest level's sweeps — and the up-legs of the
+    // levels above from + 1
+    static void downFrom(HipGridData& grid, std::size_t from, int* pending);
+    // One V-cycle rooted at `level` (its f and v set): the levels above it are not touched, no norm is taken and
+    // nothing is speculated or pipelined. The levels take the fused, tiled and coarse-launch paths they take in a
+    // whole V-cycle.
+    static void vcycleFrom(HipGridData& grid, std::size_t level);
+    // Full multigrid (nested iteration; not in the reference): every level's f becomes the full-weighting
+    // restriction of level 0's f as it stands; the start level s (fmgStartLevel) is iterated from zero and each
+    // finer level from the tricubic prolongation (gs_fmg_prolong) of the level below, cyclesPerLevel V-cycles
+    // each. Overwrites v on every level; returns the level-0 residual norm. LINEAR and NONLINEAR (FAS) grids on
+    // one GPU whose coarse grids align (sizes 2^k - 1); otherwise throws before any work (fmgCheck).
+    static double fmg(HipGridData& grid, int cyclesPerLevel);
+    // the deepest level such that every transition above it is gs_fmg_prolong_supported; 0: FMG not applicable
+    static std::size_t fmgStartLevel(const HipGridData& grid);
+    static void fmgCheck(const HipGridData& grid, int cyclesPerLevel); // throws what fmg would
+    static void fmgRun(HipGridData& grid, int cyclesPerLevel);         // fmg without the closing norm
     // Up to maxCycles V-cycles with the host's wait for cycle i's norm overlapped with cycle i+1's
     // cycleDown (when pipelinable): onNorm(i, res) gets each closing norm in order and returns true
     // to stop — the early-enqueued work then only wrote coarse levels and scratch, and the adoption

@@ -613,6 +613,41 @@ int gs_prolong_add(const double* coarse_v, const double* coarse_sub, const gs_le
     return launch_status();
 }
 
+int gs_fmg_prolong_supported(const gs_level* cl, const gs_level* fl)
+{
+    return (!bad_level(cl) && !bad_level(fl) && cl->z0 == 0 && fl->z0 == 0 && cl->nx >= 1 && cl->ny >= 1 &&
+            cl->nz >= 1 && fl->nx == 2 * cl->nx + 1 && fl->ny == 2 * cl->ny + 1 && fl->nz == 2 * cl->nz + 1)
+               ? 1
+               : 0;
+}
+
+int gs_fmg_prolong(const double* coarse, const gs_level* cl, double* fine, const gs_level* fl, hipStream_t st)
+{
+    if (!coarse || !fine || !gs_fmg_prolong_supported(cl, fl)) return GS_EINVAL;
+    // non-temporal fine stores for a stream larger than the Infinity Cache (GS_FMG_NT forces either, A/B)
+    const bool nt = kKnobs.fmgNt < 0 ? fl->nx * fl->ny * fl->nz >= ((int64_t)1 << 25) : kKnobs.fmgNt != 0;
+    // z-cells per block: 8 on levels that do not fill the chip, else the chunk of 8..64 that makes the grid whole
+    // rounds of resident blocks (fit_chunk; each chunk stages three planes more than it has cells)
+    const int64_t cells = cl->nz + 1;
+    const int64_t tiles = ((cl->nx + FP_TX) / FP_TX) * ((cl->ny + FP_TY) / FP_TY);
+    const void* fn = nt ? (const void*)k_fmg_prolong<true> : (const void*)k_fmg_prolong<false>;
+    int zc = fit_chunk(tiles, cells, resident_blocks(fn, FP_TX * FP_TY), 8, 64, false, 3.0);
+    if (zc < 8) zc = tiles >= 256 && cells >= 128 ? 32 : 8; // (GS_FIT_ROUNDS=0)
+    const dim3 g((unsigned)((cl->nx + FP_TX) / FP_TX), (unsigned)((cl->ny + FP_TY) / FP_TY),
+                 (unsigned)((cells + zc - 1) / zc)),
+        b(FP_TX, FP_TY);
+    if (g.y > 65535u || g.z > 65535u) return GS_EINVAL;
+    // the fine pair (2i+1, 2i+2) as one 16-byte store where the layout aligns it (gs_field_layout does)
+    const int al = ((reinterpret_cast<uintptr_t>(fine + 1) & 15) == 0 && fl->ldy % 2 == 0 && fl->ldz % 2 == 0) ? 1 : 0;
+    if (nt)
+        hipLaunchKernelGGL(k_fmg_prolong<true>, g, b, 0, st, coarse, fine, (int)cl->nx, (int)cl->ny, (int)cl->nz,
+                           cl->ldy, cl->ldz, fl->ldy, fl->ldz, zc, al);
+    else
+        hipLaunchKernelGGL(k_fmg_prolong<false>, g, b, 0, st, coarse, fine, (int)cl->nx, (int)cl->ny, (int)cl->nz,
+                           cl->ldy, cl->ldz, fl->ldy, fl->ldz, zc, al);
+    return launch_status();
+}
+
 int gs_apply_op(const gs_stencil* S, const gs_level* L, double gamma, const double* u, double* out, hipStream_t st)
 {
     if (!out) return GS_EINVAL;
@@ -806,7 +841,8 @@ const char* gs_build_info(void)
            "loaded first, non-temporal unshared rows), NEWTON update + "
            "compF (+ level-1 restriction, + the next factor B), NEWTON inner solves on B (GS_NEWTON_B: reciprocal "
            "quotient, shared per pair; GS_NEWTON_G: B = gamma unread), unit-neighbour stencil sums, tiled small levels, "
-           "one-workgroup coarse cycle; fp-contract=off";
+           "one-workgroup coarse cycle; full-multigrid start (GS_FMG=k, gs_grid_fmg): tricubic gs_fmg_prolong "
+           "(k_fmg_prolong: z-march, coarse planes staged in LDS, 16-byte fine stores); fp-contract=off";
 }
 
 } // extern "C"

@@ -155,6 +155,10 @@ class HipGridData:
     def stream(self) -> int:
         return driver().gs_grid_stream(self.handle)
 
+    def fmg_start_level(self) -> int:
+        """The level HipSolver.fmg starts on; 0 when full multigrid is not applicable to this grid."""
+        return driver().gs_grid_fmg_start_level(self.handle)
+
     def field(self, level: int, name: str) -> np.ndarray:
         """Copy of a padded field as a dense array indexed [x][y][z] (the reference's axis order)."""
         g = self.getLevel(level).geom
@@ -215,6 +219,21 @@ class HipSolver:
     def vcycle(grid: HipGridData) -> float:
         r = C.c_double()
         _check(driver().gs_grid_vcycle(grid.handle, C.byref(r)))
+        return r.value
+
+    @staticmethod
+    def vcycle_from(grid: HipGridData, level: int):
+        """One V-cycle rooted at `level` (its f and v as they stand); the levels above it are not touched."""
+        _check(driver().gs_grid_vcycle_level(grid.handle, level))
+
+    @staticmethod
+    def fmg(grid: HipGridData, cycles_per_level: int = 1) -> float:
+        """Full multigrid start: coarse right-hand sides restricted from level 0's f, the start level iterated from
+        zero, every finer level from the tricubic prolongation of the level below, `cycles_per_level` V-cycles
+        each. Overwrites v on every level; returns the level-0 residual norm. Raises GpuSolveError where FMG is
+        not applicable (sizes other than 2^k - 1, NEWTON mode, Z-slab grids, cycles_per_level < 1)."""
+        r = C.c_double()
+        _check(driver().gs_grid_fmg(grid.handle, cycles_per_level, C.byref(r)))
         return r.value
 
     @staticmethod

@@ -95,6 +95,8 @@ KERNEL_API = {
     "gs_interpolate": (C.c_int, [C.c_void_p, C.POINTER(gs_level), C.c_void_p, C.POINTER(gs_level), C.c_void_p]),
     "gs_prolong_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(gs_level), C.c_void_p, C.POINTER(gs_level),
                                  C.c_void_p]),
+    "gs_fmg_prolong_supported": (C.c_int, [C.POINTER(gs_level), C.POINTER(gs_level)]),
+    "gs_fmg_prolong": (C.c_int, [C.c_void_p, C.POINTER(gs_level), C.c_void_p, C.POINTER(gs_level), C.c_void_p]),
     "gs_apply_op": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_double, C.c_void_p, C.c_void_p,
                               C.c_void_p]),
     "gs_apply_op_add": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_double, C.c_void_p, C.c_void_p,
@@ -128,6 +130,9 @@ DRIVER_API = {
     "gs_grid_destroy": (None, [C.c_void_p]),
     "gs_grid_solve": (C.c_int, [C.c_void_p, C.c_int, dptr, C.c_int, C.POINTER(C.c_int)]),
     "gs_grid_vcycle": (C.c_int, [C.c_void_p, dptr]),
+    "gs_grid_vcycle_level": (C.c_int, [C.c_void_p, C.c_int]),
+    "gs_grid_fmg": (C.c_int, [C.c_void_p, C.c_int, dptr]),
+    "gs_grid_fmg_start_level": (C.c_int, [C.c_void_p]),
     "gs_grid_jacobi": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "gs_grid_residual_norm": (C.c_int, [C.c_void_p, C.c_int, dptr]),
     "gs_grid_num_levels": (C.c_int, [C.c_void_p]),

@@ -48,6 +48,22 @@ void gs_grid_destroy(void* grid);
 int gs_grid_solve(void* grid, int print, double* hist, int cap, int* count);
 
 int gs_grid_vcycle(void* grid, double* residual);
+/* One V-cycle rooted at `level` (added): the down-leg, coarse end and up-leg of gs_grid_vcycle with level `level`
+ * in level 0's place — its f and v are the caller's, the levels above it are not touched, no norm is taken. The
+ * same fused, tiled and coarse-launch paths as inside a whole V-cycle. Single-GPU grids. */
+int gs_grid_vcycle_level(void* grid, int level);
+/* Full multigrid start (added; nested iteration): every level's f becomes the full-weighting restriction of level
+ * 0's f as it stands (an uploaded f is honoured); the start level (gs_grid_fmg_start_level) is iterated from zero
+ * and every finer level from the tricubic prolongation (gs_fmg_prolong) of the level below, cycles_per_level
+ * V-cycles each. Overwrites v on every level; *residual = the level-0 residual norm. LINEAR and NONLINEAR (FAS)
+ * grids. Fails, with nothing done and the reason in gs_last_error(): a grid whose coarse grids do not align (any
+ * axis not 2^k - 1: e.g. every power-of-two size), NEWTON mode, a Z-slab / RCCL grid, cycles_per_level < 1.
+ * GS_FMG=k in the environment when the grid is created makes gs_grid_solve / GpuSolve-hip run this pass after the
+ * initial-residual line. */
+int gs_grid_fmg(void* grid, int cycles_per_level, double* residual);
+/* The level FMG starts on: the deepest level with every transition above it aligned (fine n = 2 coarse n + 1 per
+ * axis); 0 when FMG is not applicable to the grid. */
+int gs_grid_fmg_start_level(void* grid);
 int gs_grid_jacobi(void* grid, int level, int sweeps);
 int gs_grid_residual_norm(void* grid, int level, double* norm);
 int gs_grid_num_levels(void* grid);

@@ -218,6 +218,22 @@ int gs_interpolate(const double* coarse, const gs_level* cl, double* e, const gs
 int gs_prolong_add(const double* coarse_v, const double* coarse_sub, const gs_level* cl, double* fine_v,
                    const gs_level* fl, hipStream_t stream);
 
+/* Full multigrid's prolongation of a SOLUTION (added; not a reference operator): tricubic, where gs_interpolate /
+ * gs_prolong_add are trilinear and meant for corrections. Supported (gs_fmg_prolong_supported == 1) for whole
+ * levels (z0 = 0) with fine n = 2 * coarse n + 1 on every axis, so that padded fine index 2i is coarse index i. The
+ * coarse boundary ring (the zero Dirichlet value) takes part as data; every fine INTERIOR point is written and the
+ * fine ring is left alone. Anything else, or a null pointer: GS_EINVAL.
+ * The operator is separable and evaluated x, then y, then z (three roundings per point, no contraction), per axis:
+ *   even fine index 2i                   c[i]
+ *   odd fine index 2i+1, 1 <= i <= n-1   (((-c[i-1] + 9*c[i]) + 9*c[i+1]) - c[i+2]) / 16
+ *   the first odd index (i = 0)          (((5*c[0] + 15*c[1]) - 5*c[2]) + c[3]) / 16
+ *   the last odd index (i = n)           the mirror image: c[n+1], c[n], c[n-1], c[n-2]
+ *   n = 1 (three padded values)          ((3*c[0] + 6*c[1]) - c[2]) / 8 and its mirror
+ * so a numpy restatement of the three passes reproduces it bit for bit (tests/fmg_ref.py). No read touches memory
+ * outside the padded coarse array. */
+int gs_fmg_prolong_supported(const gs_level* coarse, const gs_level* fine);
+int gs_fmg_prolong(const double* coarse, const gs_level* cl, double* fine, const gs_level* fl, hipStream_t stream);
+
 /* out = A(u)/h^2 + gamma*u*exp(u) on the interior (FAS coarse operator). */
 int gs_apply_op(const gs_stencil* S, const gs_level* L, double gamma, const double* u, double* out,
                 hipStream_t stream);
