@@ -299,6 +299,8 @@ __device__ __forceinline__ void div_hh_row(const Coef& k, double (&q)[2])
 // by -1 is a sign flip, and IEEE subtraction is the addition of the negation), and the first term
 // 0.0 + s0 * c equals fma(s0, c, 0.0): both round the product once and add an exact zero, and with
 // |s0| >= 1 a non-zero product never underflows to a signed zero (the one case where they differ).
+// (A NaN operand's sign is the one thing that differs: s - x negates it, s + (-1) * x does not. Every kernel,
+// k_generic included, takes this form for a unit stencil, so they agree with one another on those bits too.)
 template <bool UN = false>
 __device__ __forceinline__ double stencil_sum(const Coef& k, double c, double xp, double xm, double yp, double ym,
                                               double zp, double zm)
@@ -321,6 +323,34 @@ __device__ __forceinline__ double stencil_sum(const Coef& k, double c, double xp
     s += k.s[4] * ym;
     s += k.s[5] * zp;
     s += k.s[6] * zm;
+    return s;
+}
+
+// stencil_sum<false> with each addition's operands held in the source order (sum, product): where both are NaNs the
+// hardware returns the first operand's, and the compiler is free to commute an addition, which it does in k_tb3y and
+// does not in the one-point kernel; every other value is the same either way. (The unit form needs no such care:
+// a - b keeps its operand order.) k_tb3y's general-stencil instance only.
+__device__ __forceinline__ double add_in_order(double a, double b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    double r;
+    asm("v_add_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+#else
+    return a + b;
+#endif
+}
+__device__ __forceinline__ double stencil_sum_in_order(const Coef& k, double c, double xp, double xm, double yp,
+                                                       double ym, double zp, double zm)
+{
+    double s = 0.0;
+    s += k.s[0] * c;
+    s = add_in_order(s, k.s[1] * xp);
+    s = add_in_order(s, k.s[2] * xm);
+    s = add_in_order(s, k.s[3] * yp);
+    s = add_in_order(s, k.s[4] * ym);
+    s = add_in_order(s, k.s[5] * zp);
+    s = add_in_order(s, k.s[6] * zm);
     return s;
 }
 
@@ -895,8 +925,17 @@ __global__ __launch_bounds__(256) void k_generic(Coef k, const double* __restric
     if (x <= nx && y <= ny) {
         const int64_t p = x + y * ldy + (int64_t)z * ldz;
         double s = 0.0;
+        if (k.unit) {
+            // stencil_sum<true>'s form, term by term in the stencil's order: the same value bit for bit (see there), and
+            // the NaN bits too are then those of the unit-stencil kernels of the large levels, the pairs and the
+            // triples: s - x negates a NaN operand's sign, s + (-1) * x does not
+            s = __builtin_fma(k.s[0], v ? v[p + k.off[0]] : 0.0, 0.0);
 #pragma unroll
-        for (int i = 0; i < 7; i++) s += k.s[i] * (v ? v[p + k.off[i]] : 0.0);
+            for (int i = 1; i < 7; i++) s = s - (v ? v[p + k.off[i]] : 0.0);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 7; i++) s += k.s[i] * (v ? v[p + k.off[i]] : 0.0);
+        }
         s = div_hh(k, s);
         const double c = v ? v[p] : 0.0;
         const double wv = newtonish(MODE) ? w[p] : 0.0;
@@ -3269,11 +3308,12 @@ bool tbx_pfd2() { return kKnobs.tbxPfd2; }
 // sweep-1(z-1), sweep-2(z-2)), rows <= 0 recomputed halo. v is loaded on rows -2..RY (row -2 at plane z only), f on
 // rows -1..RY; sweep 1 is evaluated on rows -1..RY, sweep 2 on rows 0..RY, sweep 3 on rows 1..RY: 9 row evaluations
 // per y-wave and step for 2 output rows. One plane step of prefetch (two operand slots), loads grouped by field,
-// one LDS-only barrier per step, the x-edge columns of every stage through `edge` into SGPRs.
+// one LDS-only barrier per step, the x-edge columns of every stage through `edge`: each row reads its two edge values
+// where it uses them, straight into the VGPRs the DPP shift takes as its old operand (no readfirstlane, no copy back).
 // State a lane only re-reads itself one or two steps later lives in LDS, not in registers (k_tb2y's wprev_l / fprev_l
 // pattern, no barrier): f of planes z-1 / z-2 for sweeps 2 / 3 and the previous-plane rows of sweeps 1 / 2. With that
-// state in registers, or with the edge values in VGPRs as the LINEAR pair keeps them, every instance spills
-// (DESIGN.md §4.1).
+// state in registers, or with all the edge values read into VGPRs up front as the LINEAR pair keeps them, every
+// instance spills.
 // A chunk recomputes three prologue steps (z = zb-2 .. zb), whose stage values are formed from whatever the
 // zero-initialised state gives and are never consumed by a stored value. Boundary rows, columns and planes keep the
 // input value at every stage; plane addresses are clamped to 0..nz+1. Every point goes through the expressions of the
@@ -3281,8 +3321,8 @@ bool tbx_pfd2() { return kKnobs.tbxPfd2; }
 // Whole non-distributed levels only (no ghost-plane sides), a real input iterate, no prolongation, no norm partials.
 // DB: the stencil sums of several rows are divided by h^2 in ONE batch (div_hh_mm over two rows of sweep 1, every row
 // of sweeps 2 and 3: four range branches per step instead of nine, and the rows' dependent chains interleave); else
-// row by row. Each quotient is the same value either way. The unit-stencil instances are batched (252 VGPRs), the
-// general-stencil instance is not (242; batched it spills).
+// row by row. Each quotient is the same value either way. The unit-stencil instances are batched (252 / 256 VGPRs),
+// the general-stencil instance is not (254, its sums through stencil_sum_in_order; batched it spills).
 template <bool UN, bool FX, bool DB>
 __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double* __restrict__ v,
                                                            const double* __restrict__ f, double* __restrict__ out,
@@ -3394,12 +3434,10 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
             yrow[ph][wy][wx][2][lane] = S2c[N1 - 1];
             // LDS-only barrier: the outstanding prefetch stays in flight across it
             GS_LDS_BARRIER();
-            double CL[NE], CR[NE];
-#pragma unroll
-            for (int i = 0; i < NE; i++) { // wave-uniform: kept in SGPRs
-                CL[i] = uniform_d(edge[ph][wy][wx][1][i]);
-                CR[i] = uniform_d(edge[ph][wy][wx + 2][0][i]);
-            }
+            // the x-edge values of the neighbour waves: read where a row uses them (an LDS broadcast read straight into
+            // the VGPRs the DPP shift takes as its old operand; all NE pairs read up front spill)
+            const double* const CL = edge[ph][wy][wx][1];
+            const double* const CR = edge[ph][wy][wx + 2][0];
             const double2 vY = yrow[ph][wy ^ 1][wx][0][lane];  // v(z) at local row RY+1
             const double2 s1Y = yrow[ph][wy ^ 1][wx][1][lane]; // sweep-1(z-1) at local row RY+1
             const double2 s2Y = yrow[ph][wy ^ 1][wx][2][lane]; // sweep-2(z-2) at local row RY+1
@@ -3412,8 +3450,13 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
                 const double2 ym = M ? lp : lm, yp = M ? lm : lp;
                 const double xm0 = lane_from_left<true>(c.y, el);
                 const double xp1 = lane_from_right<true>(c.x, er);
-                q0 = stencil_sum<UN>(k, c.x, c.y, xm0, yp.x, ym.x, zp.x, zm.x);
-                q1 = stencil_sum<UN>(k, c.y, xp1, c.x, yp.y, ym.y, zp.y, zm.y);
+                if constexpr (UN) {
+                    q0 = stencil_sum<true>(k, c.x, c.y, xm0, yp.x, ym.x, zp.x, zm.x);
+                    q1 = stencil_sum<true>(k, c.y, xp1, c.x, yp.y, ym.y, zp.y, zm.y);
+                } else {
+                    q0 = stencil_sum_in_order(k, c.x, c.y, xm0, yp.x, ym.x, zp.x, zm.x);
+                    q1 = stencil_sum_in_order(k, c.y, xp1, c.x, yp.y, ym.y, zp.y, zm.y);
+                }
             };
             auto row_finish = [&](const double2 c, const double q0, const double q1, const double2 fv) {
                 const double a0 = op_finish<MODE>(k, q0, c.x, 0.0);

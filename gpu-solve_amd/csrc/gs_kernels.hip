@@ -832,8 +832,9 @@ const char* gs_strerror(int code)
 
 const char* gs_build_info(void)
 {
-    return "gpusolve_hip v14: LINEAR triples k_tb3y(the pair's whole-row tile, three sweeps per pass, one-step prefetch, "
-           "per-lane f / previous-plane rows in LDS), pairs k_tb2y(4x2 waves, 2 rows/wave, one round of z-chunks on large levels, LINEAR 2-step prefetch; +prolong; "
+    return "gpusolve_hip v15: LINEAR triples k_tb3y(the pair's whole-row tile, three sweeps per pass, one-step prefetch, "
+           "per-lane f / previous-plane rows in LDS, x-edge values read row by row from LDS into the DPP shift), "
+           "pairs k_tb2y(4x2 waves, 2 rows/wave, one round of z-chunks on large levels, LINEAR 2-step prefetch; +prolong; "
            "512-point column blocks for longer rows in every mode; from 64^3 levels; zero-iterate chunks fitted to "
            "resident rounds; zero iterates q = +0; whole-wave rows without range selects (FX); LINEAR loads grouped by "
            "field; x-edge values in VGPRs for LINEAR and the NEWTON_B whole-row plain pair), sweeps k_rb(ry2 w4 zc<=32 "
