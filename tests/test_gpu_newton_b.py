@@ -190,7 +190,8 @@ def test_mode_g_matches_mode_b_on_a_gamma_field(dims, gamma):
     for tag, mode, wf in (("b", NEWTON_B, g_field), ("g", NEWTON_G, g_field), ("gnan", NEWTON_G, nan_field)):
         o = outs[tag] = {}
         o["sweep"] = DevField(*dims, fill=0.0)
-        if tag != "gnan":  # one sweep / the residual read the field (k_rb)
+        if tag != "gnan":  # one sweep / the residual read the field (k_generic at these shapes: all lie below
+            # pass_plan's 1024-block threshold; k_rb reads it too, tests/test_gpu_rb_pass.py runs its mode 3)
             ok(k().gs_jacobi_sweep(C.byref(S), C.byref(L), mode, 0.8, gamma, v.ptr, o["sweep"].ptr, f.ptr, wf.ptr,
                                    st()))
             o["res"] = DevField(*dims, fill=0.0)
