@@ -183,6 +183,38 @@ int gs_grid_fmg(void* grid, int cycles_per_level, double* residual)
 
 int gs_grid_fmg_start_level(void* grid) { return (int)gs::HipSolver::fmgStartLevel(G(grid)); }
 
+int gs_grid_set_weights(void* grid, const double* pre, int npre, const double* post, int npost)
+{
+    return guarded([&] { G(grid).setWeights(pre, npre, post, npost); });
+}
+
+int gs_grid_get_weights(void* grid, double* pre, double* post)
+{
+    const auto& g = G(grid);
+    if (!g.weighted()) return 0;
+    for (std::size_t i = 0; pre && i < g.preSmoothing; i++) pre[i] = g.wPre()[i];
+    for (std::size_t i = 0; post && i < g.postSmoothing; i++) post[i] = g.wPost()[i];
+    return 1;
+}
+
+int gs_chebyshev_weights(int nu, double lo, double hi, double* out)
+{
+    return guarded([&] {
+        if (!out) throw gs::Error("chebyshev weights: null output");
+        const std::vector<double> w = gs::chebyshevWeights(nu, lo, hi);
+        std::copy(w.begin(), w.end(), out);
+    });
+}
+
+int gs_parse_omegas(const char* text, int pre, int post, double* out)
+{
+    return guarded([&] {
+        if (!text || pre < 0 || post < 0) throw gs::Error("GS_OMEGAS: null text or a negative count");
+        const std::vector<double> w = gs::parseOmegas(text, (std::size_t)pre, (std::size_t)post);
+        if (out) std::copy(w.begin(), w.end(), out);
+    });
+}
+
 int gs_grid_jacobi(void* grid, int level, int sweeps)
 {
     return guarded([&] { gs::HipSolver::jacobi(G(grid), (std::size_t)level, (std::size_t)sweeps); });

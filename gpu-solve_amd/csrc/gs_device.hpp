@@ -73,7 +73,7 @@ struct RtBool {
 struct Coef {
     double s[7];
     double hh;     // h*h
-    double omega;
+    double omega[3]; // relaxation weight of each fused stage (sweep) of a pass; equal unless weights were given
     double gamma;
     double alpha;  // h*h / s0          (CpuSolver.cpp:145)
     double preFac; // s0 / (h*h)        (CpuSolver.cpp:144)
@@ -176,7 +176,7 @@ Coef make_coef(const gs_stencil* S, const gs_level* L, double omega, double gamm
         k.off[i] = S->ox[i] + S->oy[i] * L->ldy + S->oz[i] * L->ldz;
     }
     k.hh = L->h * L->h;
-    k.omega = omega;
+    for (int i = 0; i < 3; i++) k.omega[i] = omega;
     k.gamma = gamma;
     k.alpha = k.hh / S->s[0];
     k.preFac = S->s[0] / k.hh;
@@ -190,6 +190,14 @@ Coef make_coef(const gs_stencil* S, const gs_level* L, double omega, double gamm
 #ifdef GS_EXP_EFIELD
     k.efoff = gs_exp_efoff;
 #endif
+    return k;
+}
+
+// the same with one relaxation weight per fused stage (n <= 3 of them; the remaining stages repeat the last)
+Coef make_coef_w(const gs_stencil* S, const gs_level* L, const double* omegas, int n, double gamma, int bconst = 0)
+{
+    Coef k = make_coef(S, L, omegas[0], gamma, bconst);
+    for (int i = 1; i < 3; i++) k.omega[i] = omegas[i < n ? i : n - 1];
     return k;
 }
 
@@ -410,15 +418,21 @@ __device__ __forceinline__ double nb_quot(double r, double den)
 }
 
 // Jacobi point update from the old value and its residual — CpuSolver.cpp:157-171
+// (om: the relaxation weight of the sweep the point belongs to, a wave-uniform scalar: k.omega[stage])
 template <int MODE>
-__device__ __forceinline__ double jacobi_update(const Coef& k, double v, double r, double w)
+__device__ __forceinline__ double jacobi_update(const Coef& k, double v, double r, double w, double om)
 {
-    if (MODE == GS_LINEAR) return v + k.omega * (k.alpha * r);
-    if (MODE == GS_NEWTON_B) return v + k.omega * nb_quot(r, k.preFac + w); // preFac + B: the reference's den
+    if (MODE == GS_LINEAR) return v + om * (k.alpha * r);
+    if (MODE == GS_NEWTON_B) return v + om * nb_quot(r, k.preFac + w); // preFac + B: the reference's den
     const double u = (MODE == GS_NONLINEAR) ? v : w;
     const double eu = exp(u);
     const double den = k.preFac + k.gamma * (1 + u) * eu;
-    return v + k.omega * (r / den);
+    return v + om * (r / den);
+}
+template <int MODE>
+__device__ __forceinline__ double jacobi_update(const Coef& k, double v, double r, double w)
+{
+    return jacobi_update<MODE>(k, v, r, w, k.omega[0]);
 }
 
 // NEWTON's linearisation terms of a point, A = gamma (1 + w) and E = exp(w), computed ONCE per point
@@ -427,14 +441,14 @@ __device__ __forceinline__ double jacobi_update(const Coef& k, double v, double 
 // by exp(w) last (CpuSolver.cpp:63-66, :157-171).
 __device__ __forceinline__ double newton_op(double q, double c, double A, double E) { return q + A * c * E; }
 template <int MODE>
-__device__ __forceinline__ double newton_update(const Coef& k, double v, double r, double A, double E)
+__device__ __forceinline__ double newton_update(const Coef& k, double v, double r, double A, double E, double om)
 {
     const double den = k.preFac + A * E;
-    if constexpr (MODE == GS_NEWTON_B) return v + k.omega * nb_quot(r, den); // (E = 1: den = preFac + B exactly)
+    if constexpr (MODE == GS_NEWTON_B) return v + om * nb_quot(r, den); // (E = 1: den = preFac + B exactly)
 #ifdef GS_EXP_NODIV
-    return v + k.omega * (r * den);
+    return v + om * (r * den);
 #else
-    return v + k.omega * (r / den);
+    return v + om * (r / den);
 #endif
 }
 
@@ -678,8 +692,8 @@ __global__ __launch_bounds__(WAVE* W) void k_rb(Coef k, const double* __restrict
                 }
                 double o0, o1;
                 if (NS) {
-                    o0 = newton_update<MODE>(k, c.x, r0, Ax, Ex);
-                    o1 = newton_update<MODE>(k, c.y, r1, Ay, Ey);
+                    o0 = newton_update<MODE>(k, c.x, r0, Ax, Ex, k.omega[0]);
+                    o1 = newton_update<MODE>(k, c.y, r1, Ay, Ey, k.omega[0]);
                 } else if (KIND == 0) {
                     o0 = jacobi_update<MODE>(k, c.x, r0, wx);
                     o1 = jacobi_update<MODE>(k, c.y, r1, wy);
@@ -943,7 +957,7 @@ __global__ __launch_bounds__(256) void k_generic(Coef k, const double* __restric
         if (KIND == 0) {
             const double r = f[p] - s;
             sumsq = r * r;
-            out[p] = jacobi_update<MODE>(k, c, r, wv);
+            out[p] = jacobi_update<MODE>(k, c, r, wv, k.omega[0]);
         } else if (KIND == 1) {
             const double r = f[p] - s;
             sumsq = r * r;
@@ -1814,9 +1828,9 @@ constexpr int TS = 8, TS_T = 1024; // 1024 threads: ~3 points per thread and sta
 // one Jacobi sweep over a tile: dst (edge dN) from src (edge dN + 2; dst i <-> src i + 1), f (and, NEWTON,
 // the linearisation point w) from tiles of edge fN (dst i <-> f i + fo); global index of dst point 0: g0
 template <int MODE, bool UN>
-__device__ __forceinline__ void tile_sweep(const Coef& k, const double* src, double* dst, int dN, const double* F,
-                                           const double* W, int fN, int fo, int gx0, int gy0, int gz0, int nx, int ny,
-                                           int nz)
+__device__ __forceinline__ void tile_sweep(const Coef& k, double om, const double* src, double* dst, int dN,
+                                           const double* F, const double* W, int fN, int fo, int gx0, int gy0, int gz0,
+                                           int nx, int ny, int nz)
 {
     const int sN = dN + 2, total = dN * dN * dN;
     for (int t = threadIdx.x; t < total; t += TS_T) {
@@ -1830,7 +1844,7 @@ __device__ __forceinline__ void tile_sweep(const Coef& k, const double* src, dou
             const double w = newtonish(MODE) ? W[qf] : 0.0;
             const double a = op_value<MODE, UN>(k, c, src[q + 1], src[q - 1], src[q + sN], src[q - sN],
                                                  src[q + sN * sN], src[q - sN * sN], w);
-            nv = jacobi_update<MODE>(k, c, F[qf] - a, w);
+            nv = jacobi_update<MODE>(k, c, F[qf] - a, w, om);
         }
         dst[t] = nv;
     }
@@ -1871,9 +1885,9 @@ __global__ __launch_bounds__(TS_T) void k_tile_pre_rr(Coef k, const double* __re
     tile_load<false>(f, sf, NF, tx - 2, ty - 2, tz - 2, nx, ny, nz, ldy, ldz);
     if (newtonish(MODE)) tile_load<false>(w, sw, NF, tx - 2, ty - 2, tz - 2, nx, ny, nz, ldy, ldz);
     __syncthreads();
-    tile_sweep<MODE, UN>(k, sv, s1, N1, sf, sw, NF, 0, tx - 2, ty - 2, tz - 2, nx, ny, nz);
+    tile_sweep<MODE, UN>(k, k.omega[0], sv, s1, N1, sf, sw, NF, 0, tx - 2, ty - 2, tz - 2, nx, ny, nz);
     __syncthreads();
-    tile_sweep<MODE, UN>(k, s1, s2, N2, sf, sw, NF, 1, tx - 1, ty - 1, tz - 1, nx, ny, nz);
+    tile_sweep<MODE, UN>(k, k.omega[1], s1, s2, N2, sf, sw, NF, 1, tx - 1, ty - 1, tz - 1, nx, ny, nz);
     __syncthreads();
     // the tile's own fine points of v'' (interior only)
     for (int t = threadIdx.x; t < TS * TS * TS; t += TS_T) {
@@ -1945,7 +1959,7 @@ __global__ __launch_bounds__(TS_T) void k_tile_pro2(Coef k, const double* __rest
     tile_load<false>(f, sf, NF, tx - 1, ty - 1, tz - 1, nx, ny, nz, ldy, ldz);
     if (newtonish(MODE)) tile_load<false>(w, sw, NF, tx - 1, ty - 1, tz - 1, nx, ny, nz, ldy, ldz);
     __syncthreads();
-    tile_sweep<MODE, UN>(k, su, s1, N1, sf, sw, NF, 0, tx - 1, ty - 1, tz - 1, nx, ny, nz);
+    tile_sweep<MODE, UN>(k, k.omega[0], su, s1, N1, sf, sw, NF, 0, tx - 1, ty - 1, tz - 1, nx, ny, nz);
     __syncthreads();
     for (int t = threadIdx.x; t < TS * TS * TS; t += TS_T) {
         const int i = t % TS, j = (t / TS) % TS, l = t / (TS * TS);
@@ -1957,7 +1971,7 @@ __global__ __launch_bounds__(TS_T) void k_tile_pro2(Coef k, const double* __rest
         const double wv = newtonish(MODE) ? sw[qf] : 0.0;
         const double a = op_value<MODE, UN>(k, cc, s1[q + 1], s1[q - 1], s1[q + N1], s1[q - N1], s1[q + N1 * N1],
                                              s1[q - N1 * N1], wv);
-        vout[gx + (int64_t)gy * ldy + (int64_t)gz * ldz] = jacobi_update<MODE>(k, cc, sf[qf] - a, wv);
+        vout[gx + (int64_t)gy * ldy + (int64_t)gz * ldz] = jacobi_update<MODE>(k, cc, sf[qf] - a, wv, k.omega[1]);
     }
 }
 
@@ -2276,6 +2290,11 @@ struct CcLevel {
 struct CcPlan {
     CcLevel L[CC_MAXLEV];
     int n, pre, post;
+    // per-sweep relaxation weights (gs_coarse_cycle_w), by value: the k-th pre-smoothing sweep of every level takes
+    // wpre[k], the k-th post-smoothing sweep wpost[k], the coarsest level's pre + post sweeps wpre then wpost.
+    // weighted == 0: every sweep takes its level's Coef::omega[0]
+    int weighted;
+    double wpre[GS_MAX_WEIGHTS], wpost[GS_MAX_WEIGHTS];
 };
 
 __device__ __forceinline__ int64_t cc_at(const CcLevel& L, int x, int y, int z)
@@ -2350,10 +2369,14 @@ __global__ __launch_bounds__(CC_T) void k_coarse_cycle(CcPlan P)
         zero &= ~(1u << l);
     };
     // `sweeps` Jacobi sweeps, residual and update fused (k_generic KIND 0), ping-pong v <-> va
-    auto smooth = [&](int l, int sweeps) {
+    // (post: the sweeps are post-smoothing sweeps; otherwise pre-smoothing sweeps, continued by the post-smoothing
+    // ones past P.pre — the coarsest level)
+    auto smooth = [&](int l, int sweeps, bool post) {
         const CcLevel& L = P.L[l];
         if (sweeps == 0) materialize(l);
         for (int s = 0; s < sweeps; s++) {
+            const int ws = post ? s + P.pre : s;
+            const double om = !P.weighted ? L.k.omega[0] : ws < P.pre ? P.wpre[ws] : P.wpost[ws - P.pre];
             const bool uz = (zero >> l) & 1;
             const double* in = cur(l);
             double* out = ((alt >> l) & 1) ? L.v : L.va;
@@ -2361,7 +2384,7 @@ __global__ __launch_bounds__(CC_T) void k_coarse_cycle(CcPlan P)
                 double c, wv;
                 const double a = cc_op<MODE>(L.k, in, uz, L.w, p, c, wv);
                 const double r = L.f[p] - a;
-                return jacobi_update<MODE>(L.k, c, r, wv);
+                return jacobi_update<MODE>(L.k, c, r, wv, om);
             });
             __syncthreads();
             alt ^= 1u << l;
@@ -2391,7 +2414,7 @@ __global__ __launch_bounds__(CC_T) void k_coarse_cycle(CcPlan P)
     // ---- down: pre-smoothing, f^2h = R(f - A v) [FAS: restV = v^2h = R v, f^2h += A(restV)] ----
     for (int l = 0; l + 1 < P.n; l++) {
         const CcLevel &F = P.L[l], &C = P.L[l + 1];
-        smooth(l, P.pre);
+        smooth(l, P.pre, false);
         const double* u = cur(l);
         cc_map(F, F.r, nullptr, [&](int, int, int, int64_t p) { // residual (k_generic KIND 1)
             double c, wv;
@@ -2412,7 +2435,7 @@ __global__ __launch_bounds__(CC_T) void k_coarse_cycle(CcPlan P)
         }
     }
     // ---- the coarsest level: pre + post sweeps (CpuSolver.cpp:117) ----
-    smooth(P.n - 1, P.pre + P.post);
+    smooth(P.n - 1, P.pre + P.post, false);
     // ---- up: v^h += P(v^2h [- restV^2h]) (k_prolong_add), post-smoothing ----
     for (int l = P.n - 1; l > 0; l--) {
         const CcLevel &C = P.L[l], &F = P.L[l - 1];
@@ -2425,7 +2448,7 @@ __global__ __launch_bounds__(CC_T) void k_coarse_cycle(CcPlan P)
             return fv[p] + e;
         });
         __syncthreads();
-        smooth(l - 1, P.post);
+        smooth(l - 1, P.post, true);
     }
 }
 
@@ -2574,8 +2597,8 @@ __global__ __launch_bounds__(WAVE* WXMAX) void k_tb2(Coef k, const double* __res
                 const double a0 = op_value<MODE>(k, c.x, c.y, xm0, yp.x, ym.x, zp.x, zm.x, wx0);
                 const double a1 = op_value<MODE>(k, c.y, xp1, c.x, yp.y, ym.y, zp.y, zm.y, wx1);
                 const double r0 = FL[cs][j - 1].x - a0, r1 = FL[cs][j - 1].y - a1;
-                const double n0 = jacobi_update<MODE>(k, c.x, r0, wx0);
-                const double n1 = jacobi_update<MODE>(k, c.y, r1, wx1);
+                const double n0 = jacobi_update<MODE>(k, c.x, r0, wx0, k.omega[0]);
+                const double n1 = jacobi_update<MODE>(k, c.y, r1, wx1, k.omega[0]);
                 if (partials && j >= 2 && j <= RY + 1 && z >= zb && z <= ze && rowc[j]) {
                     if (okx0) sumsq += r0 * r0;
                     if (okx1) sumsq += r1 * r1;
@@ -2595,8 +2618,8 @@ __global__ __launch_bounds__(WAVE* WXMAX) void k_tb2(Coef k, const double* __res
                     const double wx1 = newtonish(MODE) ? Wprev[j - 2].y : 0.0;
                     const double a0 = op_value<MODE>(k, c.x, c.y, xm0, yp.x, ym.x, zp.x, zm.x, wx0);
                     const double a1 = op_value<MODE>(k, c.y, xp1, c.x, yp.y, ym.y, zp.y, zm.y, wx1);
-                    const double o0 = jacobi_update<MODE>(k, c.x, Fprev[j - 2].x - a0, wx0);
-                    const double o1 = jacobi_update<MODE>(k, c.y, Fprev[j - 2].y - a1, wx1);
+                    const double o0 = jacobi_update<MODE>(k, c.x, Fprev[j - 2].x - a0, wx0, k.omega[1]);
+                    const double o1 = jacobi_update<MODE>(k, c.y, Fprev[j - 2].y - a1, wx1, k.omega[1]);
                     if (y0 - 2 + j <= ny) {
                         double* q = out + x + roff[j] + zo;
                         if (okx1) st2s<NT>(q, o0, o1);
@@ -3092,10 +3115,10 @@ __global__ __launch_bounds__(WAVE* WXMAX * 2, WPE > 0 ? WPE : 1) void k_tb2y(Coe
                         if constexpr (newtonish(MODE)) { // the interior rows' NEWTON expressions, exp once
                             const double we = efld(cs, 4), A = newton_A<MODE>(k, we), E = newton_E<MODE>(we);
                             const double a = newton_op(qe(), c, A, E);
-                            nv = newton_update<MODE>(k, c, efld(cs, 3) - a, A, E);
+                            nv = newton_update<MODE>(k, c, efld(cs, 3) - a, A, E, k.omega[0]);
                         } else {
                             const double a = op_finish<MODE>(k, qe(), c, 0.0);
-                            nv = jacobi_update<MODE>(k, c, EF[cs] - a, 0.0);
+                            nv = jacobi_update<MODE>(k, c, EF[cs] - a, 0.0, k.omega[0]);
                         }
                         ES1n = (!pz || !erowc) ? c : nv;
                     }
@@ -3143,19 +3166,19 @@ __global__ __launch_bounds__(WAVE* WXMAX * 2, WPE > 0 ? WPE : 1) void k_tb2y(Coe
                         if constexpr (YSH) {
                             a0 = newton_op(q[0], c.x, A.x, 1.0);
                             a1 = newton_op(q[1], c.y, A.y, 1.0);
-                            n0 = c.x + k.omega * ((FL[cs][j].x - a0) * E.x);
-                            n1 = c.y + k.omega * ((FL[cs][j].y - a1) * E.y);
+                            n0 = c.x + k.omega[0] * ((FL[cs][j].x - a0) * E.x);
+                            n1 = c.y + k.omega[0] * ((FL[cs][j].y - a1) * E.y);
                         } else {
                             a0 = newton_op(q[0], c.x, A.x, E.x);
                             a1 = newton_op(q[1], c.y, A.y, E.y);
-                            n0 = newton_update<MODE>(k, c.x, FL[cs][j].x - a0, A.x, E.x);
-                            n1 = newton_update<MODE>(k, c.y, FL[cs][j].y - a1, A.y, E.y);
+                            n0 = newton_update<MODE>(k, c.x, FL[cs][j].x - a0, A.x, E.x, k.omega[0]);
+                            n1 = newton_update<MODE>(k, c.y, FL[cs][j].y - a1, A.y, E.y, k.omega[0]);
                         }
                     } else {
                         a0 = op_finish<MODE>(k, q[0], c.x, 0.0);
                         a1 = op_finish<MODE>(k, q[1], c.y, 0.0);
-                        n0 = jacobi_update<MODE>(k, c.x, FL[cs][j].x - a0, 0.0);
-                        n1 = jacobi_update<MODE>(k, c.y, FL[cs][j].y - a1, 0.0);
+                        n0 = jacobi_update<MODE>(k, c.x, FL[cs][j].x - a0, 0.0, k.omega[0]);
+                        n1 = jacobi_update<MODE>(k, c.y, FL[cs][j].y - a1, 0.0, k.omega[0]);
                     }
                     const double r0 = FL[cs][j].x - a0, r1 = FL[cs][j].y - a1;
                     if (partials && j >= 1 && z >= zb && z <= ze && rowc[j + 1]) {
@@ -3194,17 +3217,17 @@ __global__ __launch_bounds__(WAVE* WXMAX * 2, WPE > 0 ? WPE : 1) void k_tb2y(Coe
                             const double a1 = newton_op(q[1], c.y, A.y, YSH ? 1.0 : E.y);
                             const double2 fp = RECOMP ? fprev_l[j - 1][wx + WX * wy][lane] : Fprev[j - 1];
                             if constexpr (YSH) {
-                                o0 = c.x + k.omega * ((fp.x - a0) * E.x);
-                                o1 = c.y + k.omega * ((fp.y - a1) * E.y);
+                                o0 = c.x + k.omega[1] * ((fp.x - a0) * E.x);
+                                o1 = c.y + k.omega[1] * ((fp.y - a1) * E.y);
                             } else {
-                                o0 = newton_update<MODE>(k, c.x, fp.x - a0, A.x, E.x);
-                                o1 = newton_update<MODE>(k, c.y, fp.y - a1, A.y, E.y);
+                                o0 = newton_update<MODE>(k, c.x, fp.x - a0, A.x, E.x, k.omega[1]);
+                                o1 = newton_update<MODE>(k, c.y, fp.y - a1, A.y, E.y, k.omega[1]);
                             }
                         } else {
                             const double a0 = op_finish<MODE>(k, q[0], c.x, 0.0);
                             const double a1 = op_finish<MODE>(k, q[1], c.y, 0.0);
-                            o0 = jacobi_update<MODE>(k, c.x, Fprev[j - 1].x - a0, 0.0);
-                            o1 = jacobi_update<MODE>(k, c.y, Fprev[j - 1].y - a1, 0.0);
+                            o0 = jacobi_update<MODE>(k, c.x, Fprev[j - 1].x - a0, 0.0, k.omega[1]);
+                            o1 = jacobi_update<MODE>(k, c.y, Fprev[j - 1].y - a1, 0.0, k.omega[1]);
                         }
                         if (yof(j) <= ny) {
                             double* qo = out + x + roff[j + 1] + zo;
@@ -3458,11 +3481,11 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
                     q1 = stencil_sum_in_order(k, c.y, xp1, c.x, yp.y, ym.y, zp.y, zm.y);
                 }
             };
-            auto row_finish = [&](const double2 c, const double q0, const double q1, const double2 fv) {
+            auto row_finish = [&](const double om, const double2 c, const double q0, const double q1, const double2 fv) {
                 const double a0 = op_finish<MODE>(k, q0, c.x, 0.0);
                 const double a1 = op_finish<MODE>(k, q1, c.y, 0.0);
-                return make_double2(jacobi_update<MODE>(k, c.x, fv.x - a0, 0.0),
-                                    jacobi_update<MODE>(k, c.y, fv.y - a1, 0.0));
+                return make_double2(jacobi_update<MODE>(k, c.x, fv.x - a0, 0.0, om),
+                                    jacobi_update<MODE>(k, c.y, fv.y - a1, 0.0, om));
             };
             auto kept = [&](const bool keep, const double2 c, const double2 n) {
                 return make_double2((keep || bx0) ? c.x : n.x, (keep || bx1) ? c.y : n.y);
@@ -3483,7 +3506,8 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
                                  CL[i], CR[i], q[2 * (i - b)], q[2 * (i - b) + 1]);
                     div_hh_mm(k, q);
 #pragma unroll
-                    for (int i = b; i < b + B1; i++) S1n[i] = row_finish(Vc[i], q[2 * (i - b)], q[2 * (i - b) + 1], FL[cs][i]);
+                    for (int i = b; i < b + B1; i++)
+                        S1n[i] = row_finish(k.omega[0], Vc[i], q[2 * (i - b)], q[2 * (i - b) + 1], FL[cs][i]);
                 }
                 if (!FX || !pz0 || !in1) {
 #pragma unroll
@@ -3502,7 +3526,7 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
                     div_hh_mm(k, q);
 #pragma unroll
                     for (int i = b; i < b + B2; i++)
-                        S2n[i] = row_finish(S1c[i + 1], q[2 * (i - b)], q[2 * (i - b) + 1], F1[i]);
+                        S2n[i] = row_finish(k.omega[1], S1c[i + 1], q[2 * (i - b)], q[2 * (i - b) + 1], F1[i]);
                 }
                 if (!FX || !pz1 || !in2) {
 #pragma unroll
@@ -3524,7 +3548,7 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
                         div_hh_mm(k, q);
 #pragma unroll
                         for (int j = b; j < b + B3; j++) {
-                            const double2 o = row_finish(S2c[j], q[2 * (j - b)], q[2 * (j - b) + 1], fv[j - b]);
+                            const double2 o = row_finish(k.omega[2], S2c[j], q[2 * (j - b)], q[2 * (j - b) + 1], fv[j - b]);
                             if (yof(j) <= ny) {
                                 double* qo = out + x + roff[j + 2] + zo;
                                 if (okx1) st2s<true>(qo, o.x, o.y);

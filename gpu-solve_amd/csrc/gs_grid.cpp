@@ -199,6 +199,8 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
         sw.sweep3 = !on("GS_NO_SWEEP3");
         if (const char* e = std::getenv("GS_SWEEP3_MIN_POINTS")) sw.sweep3MinPoints = std::strtoll(e, nullptr, 10);
         if (const char* e = std::getenv("GS_FMG")) sw.fmg = std::max(0, std::atoi(e));
+        // GS_OMEGAS: per-sweep relaxation weights; a malformed value or a count mismatch throws here, before any work
+        if (const char* e = std::getenv("GS_OMEGAS")) weights = parseOmegas(e, preSmoothing, postSmoothing);
     }
     std::vector<int64_t> nzs, pts;
     for (int l = 0; l < nlev; l++) {
@@ -489,6 +491,87 @@ gs_level HipGridData::ownedGeom(const LevelData& L, int64_t* off) const
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-sweep relaxation weights (pure host code)
+
+// omega_k = 1 / ((hi+lo)/2 + (hi-lo)/2 cos(pi (2k-1) / (2 nu))), k = 1..nu: the reciprocals of the roots of the
+// degree-nu Chebyshev polynomial on [lo, hi], so that prod (1 - omega_k x) is the polynomial of least maximum there
+std::vector<double> chebyshevWeights(int nu, double lo, double hi)
+{
+    if (nu < 1) throw Error("chebyshev weights: nu must be at least 1");
+    if (!(lo > 0.0) || !(hi > lo) || !std::isfinite(hi)) throw Error("chebyshev weights: need 0 < lo < hi");
+    const double pi = 3.14159265358979323846;
+    std::vector<double> w((std::size_t)nu);
+    for (int k = 1; k <= nu; k++)
+        w[(std::size_t)k - 1] = 1.0 / ((hi + lo) / 2 + (hi - lo) / 2 * std::cos(pi * (2 * k - 1) / (2.0 * nu)));
+    return w;
+}
+
+std::vector<double> checkedWeights(const double* pre, int npre, const double* post, int npost, std::size_t gridPre,
+                                   std::size_t gridPost)
+{
+    if (npre == 0 && npost == 0 && !pre && !post) return {}; // cleared
+    if (npre < 0 || npost < 0 || (npre > 0 && !pre) || (npost > 0 && !post))
+        throw Error("weights: a count is negative or its array is missing");
+    if (npre > GS_MAX_WEIGHTS || npost > GS_MAX_WEIGHTS)
+        throw Error("weights: at most " + std::to_string(GS_MAX_WEIGHTS) + " weights per leg");
+    if ((std::size_t)npre != gridPre || (std::size_t)npost != gridPost)
+        throw Error("weights: " + std::to_string(npre) + " pre / " + std::to_string(npost) +
+                    " post weights for a grid with " + std::to_string(gridPre) + " pre / " +
+                    std::to_string(gridPost) + " post smoothing sweeps");
+    std::vector<double> w;
+    for (int i = 0; i < npre; i++) w.push_back(pre[i]);
+    for (int i = 0; i < npost; i++) w.push_back(post[i]);
+    for (double x : w)
+        if (!std::isfinite(x)) throw Error("weights: every weight must be finite");
+    return w;
+}
+
+// GS_OMEGAS: "w1,w2/w3,w4" (pre weights, a slash, post weights; either side may be empty for a count of 0) or
+// "cheb" (Chebyshev weights on [1/3, 2], the 7-point operator's high-frequency band, for the grid's own counts)
+std::vector<double> parseOmegas(const char* text, std::size_t gridPre, std::size_t gridPost)
+{
+    const std::string t(text);
+    if (t == "cheb") {
+        if (gridPre > (std::size_t)GS_MAX_WEIGHTS || gridPost > (std::size_t)GS_MAX_WEIGHTS)
+            throw Error("GS_OMEGAS: at most " + std::to_string(GS_MAX_WEIGHTS) + " weights per leg");
+        std::vector<double> w;
+        if (gridPre > 0) w = chebyshevWeights((int)gridPre, 1.0 / 3.0, 2.0);
+        if (gridPost > 0) {
+            const std::vector<double> q = chebyshevWeights((int)gridPost, 1.0 / 3.0, 2.0);
+            w.insert(w.end(), q.begin(), q.end());
+        }
+        return w;
+    }
+    const std::size_t slash = t.find('/');
+    if (slash == std::string::npos || t.find('/', slash + 1) != std::string::npos)
+        throw Error("GS_OMEGAS: expected \"w1,w2/w3,w4\" or \"cheb\", got \"" + t + "\"");
+    auto list = [&](const std::string& part) {
+        std::vector<double> v;
+        std::size_t pos = 0;
+        while (!part.empty()) {
+            const std::size_t comma = part.find(',', pos);
+            const std::string item = part.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos);
+            char* end = nullptr;
+            const double x = std::strtod(item.c_str(), &end);
+            if (item.empty() || end == item.c_str() || *end != '\0')
+                throw Error("GS_OMEGAS: \"" + item + "\" is not a number (in \"" + t + "\")");
+            v.push_back(x);
+            if (comma == std::string::npos) break;
+            pos = comma + 1;
+        }
+        return v;
+    };
+    const std::vector<double> pre = list(t.substr(0, slash)), post = list(t.substr(slash + 1));
+    if (pre.empty() && post.empty()) throw Error("GS_OMEGAS: no weights in \"" + t + "\"");
+    return checkedWeights(pre.data(), (int)pre.size(), post.data(), (int)post.size(), gridPre, gridPost);
+}
+
+void HipGridData::setWeights(const double* pre, int npre, const double* post, int npost)
+{
+    weights = checkedWeights(pre, npre, post, npost, preSmoothing, postSmoothing); // (throws before assigning)
+}
+
+// ---------------------------------------------------------------------------------------------
 thread_local std::vector<double>* HipSolver::history = nullptr;
 thread_local std::vector<double>* NewtonSolver::history = nullptr;
 
@@ -496,8 +579,9 @@ namespace {
 
 // one fused sweep over local planes [z1, z2] of level L: reads L.v, writes L.vAlt; with partials,
 // also the per-block r^2 sums of the input's residual. Returns the partial count written.
+// w: the sweep's relaxation weight (per-sweep weights, HipGridData::weights); NULL: the grid's omega
 int64_t sweepPlanes(HipGridData& g, HipGridData::LevelData& L, int64_t z1, int64_t z2, hipStream_t s,
-                    double* partials = nullptr)
+                    double* partials = nullptr, const double* w = nullptr)
 {
     if (z2 < z1) return 0;
     gs_level sub = L.geom;
@@ -508,7 +592,8 @@ int64_t sweepPlanes(HipGridData& g, HipGridData::LevelData& L, int64_t z1, int64
         g.rec("sweep", {{"L", (long long)g.levelIndex(L)}, {"z1", z1}, {"z2", z2}, {"vzero", L.vZero}, {"norm", partials != nullptr}});
         return partials ? 1 : 0;
     }
-    check(gs_jacobi_sweep_norm(&g.stencilAbi, &sub, g.kmode(), g.omega, g.gamma, L.vZero ? nullptr : L.v.data() + off,
+    check(gs_jacobi_sweep_norm(&g.stencilAbi, &sub, g.kmode(), w ? w[0] : g.omega, g.gamma,
+                               L.vZero ? nullptr : L.v.data() + off,
                                L.vAlt.data() + off, L.f.data() + off, g.wOf(L) ? g.wOf(L) + off : nullptr,
                                partials, s),
           "gs_jacobi_sweep");
@@ -518,8 +603,9 @@ int64_t sweepPlanes(HipGridData& g, HipGridData::LevelData& L, int64_t z1, int64
 // two fused sweeps over local planes [z1, z2]: reads L.v (two ghost planes deep where a side is an
 // internal boundary), writes L.vAlt; with partials, also the per-block r^2 sums of the input's
 // residual. Returns the partial count written.
+// w: the two sweeps' relaxation weights; NULL: the grid's omega for both
 int64_t pairPlanes(HipGridData& g, HipGridData::LevelData& L, int64_t z1, int64_t z2, hipStream_t s,
-                   double* partials = nullptr)
+                   double* partials = nullptr, const double* w = nullptr)
 {
     if (z2 < z1) return 0;
     gs_level sub = L.geom;
@@ -534,17 +620,19 @@ int64_t pairPlanes(HipGridData& g, HipGridData::LevelData& L, int64_t z1, int64_
                        {"vzero", L.vZero}, {"norm", partials != nullptr}});
         return partials ? 1 : 0;
     }
-    check(gs_jacobi_sweep2_norm(&g.stencilAbi, &sub, g.kmode(), g.omega, g.gamma, L.vZero ? nullptr : L.v.data() + off,
-                                L.vAlt.data() + off, L.f.data() + off, g.wOf(L) ? g.wOf(L) + off : nullptr,
-                                zlo, zhi, partials, s),
+    const double om[2] = {w ? w[0] : g.omega, w ? w[1] : g.omega};
+    check(gs_jacobi_sweep2_norm_w(&g.stencilAbi, &sub, g.kmode(), om, g.gamma, L.vZero ? nullptr : L.v.data() + off,
+                                  L.vAlt.data() + off, L.f.data() + off, g.wOf(L) ? g.wOf(L) + off : nullptr,
+                                  zlo, zhi, partials, s),
           "gs_jacobi_sweep2");
     return partials ? gs_jacobi_sweep2_num_partials(&g.stencilAbi, &sub, (int)g.mode) : 0;
 }
 
 // three fused LINEAR sweeps over a whole non-distributed level (gs_jacobi_sweep3): reads L.v, writes L.vAlt
-void tripleLevel(HipGridData& g, HipGridData::LevelData& L, hipStream_t s)
+void tripleLevel(HipGridData& g, HipGridData::LevelData& L, hipStream_t s, const double* w)
 {
-    check(gs_jacobi_sweep3(&g.stencilAbi, &L.geom, g.omega, g.gamma, L.v.data(), L.vAlt.data(), L.f.data(), s),
+    const double om[3] = {w ? w[0] : g.omega, w ? w[1] : g.omega, w ? w[2] : g.omega};
+    check(gs_jacobi_sweep3_w(&g.stencilAbi, &L.geom, om, g.gamma, L.v.data(), L.vAlt.data(), L.f.data(), s),
           "gs_jacobi_sweep3");
 }
 
@@ -575,9 +663,12 @@ void proPlanes(HipGridData& g, HipGridData::LevelData& F, HipGridData::LevelData
     DeviceBuf& wb = F.proWs[s == g.stream() ? 0 : 1];
     if (wsn > wb.size()) throw Error("gs_jacobi_sweep2_prolong: workspace not sized at grid creation");
     double* ws = wsn > 0 ? wb.get(wsn) : nullptr;
-    check(gs_jacobi_sweep2_prolong_ws(&g.stencilAbi, &sub, g.kmode(), g.omega, g.gamma, F.v.data() + off,
-                                      C.v.data(), nullptr, &C.geom, F.vAlt.data() + off, F.f.data() + off,
-                                      g.wOf(F) ? g.wOf(F) + off : nullptr, zlo, zhi, ws, wsn, s),
+    // (the prolongation pair is the first two post-smoothing sweeps: post[0..1] of the per-sweep weights)
+    const double* w = g.wPost();
+    const double om[2] = {w ? w[0] : g.omega, w ? w[1] : g.omega};
+    check(gs_jacobi_sweep2_prolong_ws_w(&g.stencilAbi, &sub, g.kmode(), om, g.gamma, F.v.data() + off,
+                                        C.v.data(), nullptr, &C.geom, F.vAlt.data() + off, F.f.data() + off,
+                                        g.wOf(F) ? g.wOf(F) + off : nullptr, zlo, zhi, ws, wsn, s),
           "gs_jacobi_sweep2_prolong");
 }
 
@@ -836,7 +927,10 @@ static bool proWorthIt(HipGridData& grid, std::size_t l)
 // in order, boundary k waits exchange k-1). The interior launch is enqueued before the exchange is issued:
 // RCCL's non-blocking group is settled on the host (gs_comm.cpp), and the GPU must not wait on that host
 // round-trip between the boundary planes and the interior.
-void HipSolver::jacobi(HipGridData& grid, std::size_t l, std::size_t sweeps)
+//
+// w: a cursor into the per-sweep relaxation weights (HipGridData::weights), one weight per sweep of this call:
+// every triple, pair and single sweep takes its slice and moves the cursor on. NULL: the grid's omega throughout.
+void HipSolver::jacobi(HipGridData& grid, std::size_t l, std::size_t sweeps, const double* w)
 {
     auto& L = grid.getLevel(l);
     const hipStream_t s = grid.stream();
@@ -849,17 +943,18 @@ void HipSolver::jacobi(HipGridData& grid, std::size_t l, std::size_t sweeps)
         // pairs (3: T, 4: P P, 5: T P, 6: T T, 7: T P P, ...): never on a Z-slab, in the schedule trace or on
         // the zero iterate, which keep the pair schedule
         if (L.fusedTriples && !dist && !grid.trace && !L.vZero && (sweeps == 3 || sweeps >= 5)) {
-            tripleLevel(grid, L, s);
+            tripleLevel(grid, L, s, w);
             L.triplesRun++;
             L.v.swap(L.vAlt);
             sweeps -= 3;
+            if (w) w += 3;
             continue;
         }
         const bool pair = L.fusedPairs && sweeps >= 2;
         const int64_t b = pair ? 2 : depth; // outermost planes whose ghost copies the neighbours need
         auto run = [&](int64_t z1, int64_t z2, hipStream_t st) {
-            if (pair) pairPlanes(grid, L, z1, z2, st);
-            else sweepPlanes(grid, L, z1, z2, st);
+            if (pair) pairPlanes(grid, L, z1, z2, st, nullptr, w);
+            else sweepPlanes(grid, L, z1, z2, st, nullptr, w);
         };
         if (!dist) {
             run(1, nz, s);
@@ -911,6 +1006,7 @@ void HipSolver::jacobi(HipGridData& grid, std::size_t l, std::size_t sweeps)
         if (grid.trace) grid.rec("swap", {{"L", (long long)l}});
         L.vZero = false;
         sweeps -= pair ? 2 : 1;
+        if (w) w += pair ? 2 : 1;
     }
     if (step > 0) {
         // the last exchange (and through it the last boundary planes) before anything else on the level
@@ -946,6 +1042,10 @@ void HipSolver::coarseCycle(HipGridData& grid, std::size_t from)
     }
     if (grid.trace)
         grid.rec("coarse", {{"from", (long long)from}, {"vzero", lv[0].v_zero}});
+    else if (grid.weighted())
+        check(gs_coarse_cycle_w(&grid.stencilAbi, lv, n, grid.kmode(), grid.wPre(), grid.gamma, (int)grid.preSmoothing,
+                                (int)grid.postSmoothing, grid.stream()),
+              "gs_coarse_cycle");
     else
         check(gs_coarse_cycle(&grid.stencilAbi, lv, n, grid.kmode(), grid.omega, grid.gamma, (int)grid.preSmoothing,
                               (int)grid.postSmoothing, grid.stream()),
@@ -975,7 +1075,9 @@ double HipSolver::speculativeSweep(HipGridData& grid, int* sweeps, bool wait)
     const int depth = grid.vDepth(L);
     const int64_t b = pair ? 2 : depth;
     auto run = [&](int64_t z1, int64_t z2, hipStream_t st) {
-        n += pair ? pairPlanes(grid, L, z1, z2, st, P + n) : sweepPlanes(grid, L, z1, z2, st, P + n);
+        // (the first pre-smoothing sweeps: pre[0..] of the per-sweep weights)
+        n += pair ? pairPlanes(grid, L, z1, z2, st, P + n, grid.wPre())
+                  : sweepPlanes(grid, L, z1, z2, st, P + n, grid.wPre());
     };
     if (!(L.distributed && grid.nranks() > 1)) {
         run(1, nz, s);
@@ -1020,15 +1122,17 @@ void HipSolver::upLeg(HipGridData& grid, std::size_t i)
         materialize(grid, i - 1);
         if (grid.trace)
             grid.rec("tiledpro", {{"L", (long long)(i - 1)}});
-        else
-            check(gs_prolong_smooth2_tiled(&grid.stencilAbi, &F.geom, grid.kmode(), grid.omega, grid.gamma,
-                                           F.v.data(), C.v.data(), &C.geom, F.vAlt.data(), F.f.data(),
-                                           grid.wOf(F), s),
+        else {
+            const double* w = grid.wPost();
+            const double om[2] = {w ? w[0] : grid.omega, w ? w[1] : grid.omega};
+            check(gs_prolong_smooth2_tiled_w(&grid.stencilAbi, &F.geom, grid.kmode(), om, grid.gamma, F.v.data(),
+                                             C.v.data(), &C.geom, F.vAlt.data(), F.f.data(), grid.wOf(F), s),
                   "gs_prolong_smooth2_tiled");
+        }
         F.v.swap(F.vAlt);
         if (grid.trace) grid.rec("swap", {{"L", (long long)(i - 1)}});
         F.vZero = false;
-        jacobi(grid, i - 1, grid.postSmoothing - 2);
+        jacobi(grid, i - 1, grid.postSmoothing - 2, grid.wPost(2));
         grid.clock.mark(s, (int)(i - 1), false);
         return;
     }
@@ -1059,7 +1163,7 @@ void HipSolver::upLeg(HipGridData& grid, std::size_t i)
         F.v.swap(F.vAlt);
         if (grid.trace) grid.rec("swap", {{"L", (long long)(i - 1)}});
         F.vZero = false;
-        jacobi(grid, i - 1, grid.postSmoothing - 2);
+        jacobi(grid, i - 1, grid.postSmoothing - 2, grid.wPost(2));
         grid.clock.mark(s, (int)(i - 1), false);
         return;
     }
@@ -1071,7 +1175,7 @@ void HipSolver::upLeg(HipGridData& grid, std::size_t i)
                              F.v.data(), &F.geom, s),
               "gs_prolong_add");
     grid.halo(F, F.v, s, grid.vDepth(F));
-    jacobi(grid, i - 1, grid.postSmoothing);
+    jacobi(grid, i - 1, grid.postSmoothing, grid.wPost());
     grid.clock.mark(s, (int)(i - 1), false);
 }
 
@@ -1104,11 +1208,14 @@ void HipSolver::downFrom(HipGridData& grid, std::size_t from, int* pending)
             // a small level: the pre-smoothing pair, residual and restriction in one tiled launch
             if (grid.trace)
                 grid.rec("tiledpre", {{"L", (long long)i}, {"vzero", L.vZero}});
-            else
-                check(gs_smooth2_restrict_tiled(&grid.stencilAbi, &L.geom, grid.kmode(), grid.omega, grid.gamma,
-                                                L.vZero ? nullptr : L.v.data(), L.vAlt.data(), L.f.data(),
-                                                grid.wOf(L), C.f.data(), &C.geom, s),
+            else {
+                const double* w = grid.wPre(); // (i >= 1: no speculative sweeps, the pair is pre[0..1])
+                const double om[2] = {w ? w[0] : grid.omega, w ? w[1] : grid.omega};
+                check(gs_smooth2_restrict_tiled_w(&grid.stencilAbi, &L.geom, grid.kmode(), om, grid.gamma,
+                                                  L.vZero ? nullptr : L.v.data(), L.vAlt.data(), L.f.data(),
+                                                  grid.wOf(L), C.f.data(), &C.geom, s),
                       "gs_smooth2_restrict_tiled");
+            }
             L.v.swap(L.vAlt);
             if (grid.trace) grid.rec("swap", {{"L", (long long)i}});
             L.vZero = false;
@@ -1116,7 +1223,7 @@ void HipSolver::downFrom(HipGridData& grid, std::size_t from, int* pending)
             grid.clock.mark(s, (int)i, false);
             continue;
         }
-        jacobi(grid, i, pre);
+        jacobi(grid, i, pre, grid.wPre(grid.preSmoothing - pre)); // (past the adopted speculative sweeps)
         // f^2h = R (f^h - A v^h) in one pass: the fine residual is never stored
         bool fused = false;
         if (grid.sw.fusedRR) {
@@ -1184,7 +1291,7 @@ void HipSolver::downFrom(HipGridData& grid, std::size_t from, int* pending)
     }
     grid.clock.mark(s, (int)std::min(lc, nl - 1), true);
     if (lc < nl) coarseCycle(grid, lc);
-    else jacobi(grid, nl - 1, grid.preSmoothing + grid.postSmoothing); // coarsest "solve"
+    else jacobi(grid, nl - 1, grid.preSmoothing + grid.postSmoothing, grid.wPre()); // coarsest "solve": pre, then post weights
     grid.clock.mark(s, (int)std::min(lc, nl - 1), false);
     for (std::size_t i = last; i > from + 1; i--) upLeg(grid, i);
 }

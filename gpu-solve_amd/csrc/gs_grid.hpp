@@ -171,9 +171,21 @@ public:
         // exchange k-1 has not settled on the host yet (0, adaptive), always (1), or never (2: boundary first)
         int haloOrder = 0;
         // GS_FMG=k (default 0, off): HipSolver::solve starts with a full-multigrid pass of k V-cycles per level
-        // (HipSolver::fmg) before its first V-cycle — the one switch that changes the iterate
+        // (HipSolver::fmg) before its first V-cycle — with GS_OMEGAS (weights, below) the switches that change the
+        // iterate
         int fmg = 0;
     } sw;
+    // Per-sweep relaxation weights (gs_grid_set_weights, GS_OMEGAS): preSmoothing pre weights followed by
+    // postSmoothing post weights; empty (the default): every sweep takes omega. On every level the k-th
+    // pre-smoothing sweep of a V-cycle takes pre[k], the k-th post-smoothing sweep post[k], the coarsest level's
+    // pre + post sweeps the whole sequence. HipSolver::jacobi called without a cursor (gs_grid_jacobi) keeps omega.
+    std::vector<double> weights;
+    bool weighted() const { return !weights.empty(); }
+    const double* wPre(std::size_t k = 0) const { return weights.empty() ? nullptr : weights.data() + k; }
+    const double* wPost(std::size_t k = 0) const { return weights.empty() ? nullptr : weights.data() + preSmoothing + k; }
+    // counts must equal preSmoothing / postSmoothing and be at most GS_MAX_WEIGHTS, every weight finite;
+    // (NULL, 0, NULL, 0) clears. Throws, leaving the weights as they were.
+    void setWeights(const double* pre, int npre, const double* post, int npost);
     // levels coarseFrom .. numLevels()-1 run as ONE gs_coarse_cycle launch in every V-cycle
     // (numLevels(): none); set from GS_COARSE_POINTS at construction
     std::size_t coarseFrom = 0;
@@ -311,7 +323,7 @@ public:
     // norm is left in flight (grid.readNormEnd())
     static double speculativeSweep(HipGridData& grid, int* sweeps, bool wait = true);
     static bool speculationEnabled(const HipGridData& grid);
-    static void jacobi(HipGridData& grid, std::size_t level, std::size_t sweeps);
+    static void jacobi(HipGridData& grid, std::size_t level, std::size_t sweeps, const double* weights = nullptr);
     static void materialize(HipGridData& grid, std::size_t level); // store a pending v = 0
     // the V-cycle below level `from` (its f set) in one gs_coarse_cycle launch
     static void coarseCycle(HipGridData& grid, std::size_t from);
@@ -335,6 +347,13 @@ public:
     static bool fusedUpdate(const HipGridData& grid);
     static thread_local std::vector<double>* history;
 };
+
+// Per-sweep relaxation weights, pure host code (gs_grid.cpp). chebyshevWeights: the nu Chebyshev weights on
+// [lo, hi] (throws unless nu >= 1 and 0 < lo < hi). parseOmegas: GS_OMEGAS's value, "w1,w2/w3,w4" or "cheb", as
+// pre weights followed by post weights for a grid of pre / post smoothing sweeps (throws on a malformed value, a
+// count mismatch, a non-finite weight or more than GS_MAX_WEIGHTS weights per leg).
+std::vector<double> chebyshevWeights(int nu, double lo, double hi);
+std::vector<double> parseOmegas(const char* text, std::size_t pre, std::size_t post);
 
 // The optional machine-readable metrics line of GpuSolve-hip (GS_METRICS=1), see gs_grid.cpp.
 std::string metricsLine(const HipGridData& grid);

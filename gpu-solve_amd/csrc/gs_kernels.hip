@@ -73,6 +73,13 @@ int gs_jacobi_sweep2(const gs_stencil* S, const gs_level* L, int mode, double om
     return gs_jacobi_sweep2_norm(S, L, mode, omega, gamma, v_in, v_out, f, w, zlo, zhi, nullptr, st);
 }
 
+int gs_jacobi_sweep2_w(const gs_stencil* S, const gs_level* L, int mode, const double* omegas, double gamma,
+                       const double* v_in, double* v_out, const double* f, const double* w, int zlo, int zhi,
+                       hipStream_t st)
+{
+    return gs_jacobi_sweep2_norm_w(S, L, mode, omegas, gamma, v_in, v_out, f, w, zlo, zhi, nullptr, st);
+}
+
 const char* gs_jacobi_sweep2_kernel(const gs_stencil* S, const gs_level* L, int mode)
 {
     int zc;
@@ -98,17 +105,26 @@ int gs_jacobi_sweep2_norm(const gs_stencil* S, const gs_level* L, int mode, doub
                           const double* v_in, double* v_out, const double* f, const double* w, int zlo, int zhi,
                           double* partials, hipStream_t st)
 {
+    const double omegas[2] = {omega, omega};
+    return gs_jacobi_sweep2_norm_w(S, L, mode, omegas, gamma, v_in, v_out, f, w, zlo, zhi, partials, st);
+}
+
+int gs_jacobi_sweep2_norm_w(const gs_stencil* S, const gs_level* L, int mode, const double* omegas, double gamma,
+                            const double* v_in, double* v_out, const double* f, const double* w, int zlo, int zhi,
+                            double* partials, hipStream_t st)
+{
     int zc;
     dim3 g, b;
     bool y2 = false, xh = false;
     // GS_NEWTON_G: the GS_NEWTON_B kernels take gamma for the factor instead of loading it (Coef::bconst)
     const int bconst = mode == GS_NEWTON_G;
     mode = base_mode(mode);
-    if (!S || bad_level(L) || !valid_stencil(S) || !v_out || !f || v_in == v_out || (!v_in && mode == GS_NONLINEAR) ||
+    if (!S || !omegas || bad_level(L) || !valid_stencil(S) || !v_out || !f || v_in == v_out ||
+        (!v_in && mode == GS_NONLINEAR) ||
         (newtonish(mode) && !w) || mode < GS_LINEAR || mode > GS_NEWTON_B ||
         !tb2_plan(S, L, &zc, &g, &b, &y2, mode, &xh))
         return GS_EINVAL;
-    const Coef k = make_coef(S, L, omega, gamma, bconst);
+    const Coef k = make_coef_w(S, L, omegas, 2, gamma, bconst);
     const int nx = (int)L->nx, ny = (int)L->ny, nz = (int)L->nz;
 #define GS_TB(M, Z) hipLaunchKernelGGL((k_tb2<M, TB_RY_B, TB_WX_B, true, false, Z>), g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0, zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr)
     // LINEAR zero-iterate pairs (the first sweep of a coarse level, v = 0: the lightest variant, three
@@ -200,13 +216,20 @@ int gs_jacobi_sweep3_supported(const gs_stencil* S, const gs_level* L)
 int gs_jacobi_sweep3(const gs_stencil* S, const gs_level* L, double omega, double gamma, const double* v_in,
                      double* v_out, const double* f, hipStream_t st)
 {
+    const double omegas[3] = {omega, omega, omega};
+    return gs_jacobi_sweep3_w(S, L, omegas, gamma, v_in, v_out, f, st);
+}
+
+int gs_jacobi_sweep3_w(const gs_stencil* S, const gs_level* L, const double* omegas, double gamma, const double* v_in,
+                       double* v_out, const double* f, hipStream_t st)
+{
     int zc;
     dim3 g, b;
     bool y2 = false, xh = false;
-    if (!S || bad_level(L) || !valid_stencil(S) || L->z0 != 0 || !v_in || !v_out || !f || v_in == v_out ||
+    if (!S || !omegas || bad_level(L) || !valid_stencil(S) || L->z0 != 0 || !v_in || !v_out || !f || v_in == v_out ||
         !tb2_plan(S, L, &zc, &g, &b, &y2, GS_LINEAR, &xh) || !y2)
         return GS_EINVAL;
-    const Coef k = make_coef(S, L, omega, gamma);
+    const Coef k = make_coef_w(S, L, omegas, 3, gamma);
     const int nx = (int)L->nx, ny = (int)L->ny, nz = (int)L->nz;
 #define GS_TB3(U, X) hipLaunchKernelGGL((k_tb3y<U, X, U>), g, b, 0, st, k, v_in, f, v_out, nx, ny, nz, L->ldy, L->ldz, zc)
     // FX: rows of whole 128-point waves, as the pair's (GS_PAIR_FX=0: the general instance)
@@ -251,10 +274,29 @@ int gs_jacobi_sweep2_prolong(const gs_stencil* S, const gs_level* L, int mode, d
                                        nullptr, 0, st);
 }
 
+int gs_jacobi_sweep2_prolong_w(const gs_stencil* S, const gs_level* L, int mode, const double* omegas, double gamma,
+                               const double* v_in, const double* coarse_v, const double* coarse_sub,
+                               const gs_level* cl, double* v_out, const double* f, const double* w, int zlo, int zhi,
+                               hipStream_t st)
+{
+    return gs_jacobi_sweep2_prolong_ws_w(S, L, mode, omegas, gamma, v_in, coarse_v, coarse_sub, cl, v_out, f, w, zlo,
+                                         zhi, nullptr, 0, st);
+}
+
 int gs_jacobi_sweep2_prolong_ws(const gs_stencil* S, const gs_level* L, int mode, double omega, double gamma,
                                 const double* v_in, const double* coarse_v, const double* coarse_sub,
                                 const gs_level* cl, double* v_out, const double* f, const double* w, int zlo, int zhi,
                                 double* ws, int64_t ws_elems, hipStream_t st)
+{
+    const double omegas[2] = {omega, omega};
+    return gs_jacobi_sweep2_prolong_ws_w(S, L, mode, omegas, gamma, v_in, coarse_v, coarse_sub, cl, v_out, f, w, zlo,
+                                         zhi, ws, ws_elems, st);
+}
+
+int gs_jacobi_sweep2_prolong_ws_w(const gs_stencil* S, const gs_level* L, int mode, const double* omegas, double gamma,
+                                  const double* v_in, const double* coarse_v, const double* coarse_sub,
+                                  const gs_level* cl, double* v_out, const double* f, const double* w, int zlo, int zhi,
+                                  double* ws, int64_t ws_elems, hipStream_t st)
 {
     int zc;
     dim3 g, b;
@@ -263,8 +305,8 @@ int gs_jacobi_sweep2_prolong_ws(const gs_stencil* S, const gs_level* L, int mode
     mode = base_mode(mode);
     // coarse plane of fine local plane z: (z >> 1) + czoff, z0 even (a slab, or a plane range of one)
     const int64_t czoff = cl ? L->z0 / 2 - cl->z0 : 0;
-    if (!gs_jacobi_sweep2_prolong_supported(S, L, mode) || bad_level(cl) || czoff < 0 || !v_in || !coarse_v ||
-        !v_out || !f || v_in == v_out || (mode == GS_NONLINEAR) != (coarse_sub != nullptr) || (newtonish(mode) && !w) ||
+    if (!omegas || !gs_jacobi_sweep2_prolong_supported(S, L, mode) || bad_level(cl) || czoff < 0 || !v_in ||
+        !coarse_v || !v_out || !f || v_in == v_out || (mode == GS_NONLINEAR) != (coarse_sub != nullptr) || (newtonish(mode) && !w) ||
         (L->nx + 1) / 2 > cl->nx + 1 || (L->ny + 1) / 2 > cl->ny + 1 || (L->nz + 1) / 2 + czoff > cl->nz + 1 ||
         !tb2_plan(S, L, &zc, &g, &b, &y2, mode, &xh, true))
         return GS_EINVAL;
@@ -273,7 +315,7 @@ int gs_jacobi_sweep2_prolong_ws(const gs_stencil* S, const gs_level* L, int mode
     // the kernel indexes the coarse field from the plane under fine local plane 0
     coarse_v += czoff * cl->ldz;
     if (coarse_sub) coarse_sub += czoff * cl->ldz;
-    const Coef k = make_coef(S, L, omega, gamma, bconst);
+    const Coef k = make_coef_w(S, L, omegas, 2, gamma, bconst);
     if (xh && need > 0) {
         const int bw = 2 * WAVE * TBY_WX, nb = (int)((L->nx + bw - 1) / bw - 1);
         hipLaunchKernelGGL(k_pro_strip<false>, dim3((unsigned)((L->ny + 2 + 63) / 64), (unsigned)(L->nz + 4), (unsigned)nb),
@@ -322,12 +364,20 @@ int gs_smooth2_restrict_tiled(const gs_stencil* S, const gs_level* fl, int mode,
                               const double* v_in, double* v_out, const double* f, const double* w, double* coarse_f,
                               const gs_level* cl, hipStream_t st)
 {
+    const double omegas[2] = {omega, omega};
+    return gs_smooth2_restrict_tiled_w(S, fl, mode, omegas, gamma, v_in, v_out, f, w, coarse_f, cl, st);
+}
+
+int gs_smooth2_restrict_tiled_w(const gs_stencil* S, const gs_level* fl, int mode, const double* omegas, double gamma,
+                                const double* v_in, double* v_out, const double* f, const double* w, double* coarse_f,
+                                const gs_level* cl, hipStream_t st)
+{
     mode = base_mode(mode); // (the tiled kernels read the factor field, which holds gamma under GS_NEWTON_G)
-    if (!gs_tiled_supported(S, fl, mode) || bad_level(cl) || cl->z0 != 0 || !v_out || !f || !coarse_f ||
+    if (!omegas || !gs_tiled_supported(S, fl, mode) || bad_level(cl) || cl->z0 != 0 || !v_out || !f || !coarse_f ||
         v_in == v_out || (newtonish(mode) && !w) || cl->nx != fl->nx / 2 || cl->ny != fl->ny / 2 ||
         cl->nz != fl->nz / 2)
         return GS_EINVAL;
-    const Coef k = make_coef(S, fl, omega, gamma);
+    const Coef k = make_coef_w(S, fl, omegas, 2, gamma);
     const dim3 g((unsigned)((fl->nx + TS - 1) / TS), (unsigned)((fl->ny + TS - 1) / TS), (unsigned)((fl->nz + TS - 1) / TS));
 #define GS_TPR(M, Z, U) hipLaunchKernelGGL((k_tile_pre_rr<M, Z, U>), g, dim3(TS_T), 0, st, k, v_in, f, w, v_out, coarse_f, (int)fl->nx, (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz)
 #define GS_TPRM(M) do { \
@@ -345,12 +395,21 @@ int gs_prolong_smooth2_tiled(const gs_stencil* S, const gs_level* fl, int mode, 
                              const double* v_in, const double* coarse_v, const gs_level* cl, double* v_out,
                              const double* f, const double* w, hipStream_t st)
 {
+    const double omegas[2] = {omega, omega};
+    return gs_prolong_smooth2_tiled_w(S, fl, mode, omegas, gamma, v_in, coarse_v, cl, v_out, f, w, st);
+}
+
+int gs_prolong_smooth2_tiled_w(const gs_stencil* S, const gs_level* fl, int mode, const double* omegas, double gamma,
+                               const double* v_in, const double* coarse_v, const gs_level* cl, double* v_out,
+                               const double* f, const double* w, hipStream_t st)
+{
     mode = base_mode(mode);
-    if (!gs_tiled_supported(S, fl, mode) || bad_level(cl) || cl->z0 != 0 || !v_in || !coarse_v || !v_out || !f ||
+    if (!omegas || !gs_tiled_supported(S, fl, mode) || bad_level(cl) || cl->z0 != 0 || !v_in || !coarse_v || !v_out ||
+        !f ||
         v_in == v_out || (newtonish(mode) && !w) || (fl->nx + 1) / 2 > cl->nx + 1 || (fl->ny + 1) / 2 > cl->ny + 1 ||
         (fl->nz + 1) / 2 > cl->nz + 1)
         return GS_EINVAL;
-    const Coef k = make_coef(S, fl, omega, gamma);
+    const Coef k = make_coef_w(S, fl, omegas, 2, gamma);
     const dim3 g((unsigned)((fl->nx + TS - 1) / TS), (unsigned)((fl->ny + TS - 1) / TS), (unsigned)((fl->nz + TS - 1) / TS));
 #define GS_TP2(M, U) hipLaunchKernelGGL((k_tile_pro2<M, U>), g, dim3(TS_T), 0, st, k, v_in, coarse_v, f, w, v_out, (int)fl->nx, (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, cl->ldy, cl->ldz)
     if (mode == GS_NEWTON_B) {
@@ -778,8 +837,13 @@ int gs_axpy(double* y, const double* x, double a, int64_t n, hipStream_t st)
 
 int gs_coarse_cycle_max_levels(void) { return CC_MAXLEV; }
 
-int gs_coarse_cycle(const gs_stencil* S, const gs_coarse_level* lv, int n, int mode, double omega, double gamma,
-                    int pre, int post, hipStream_t st)
+int gs_max_weights(void) { return GS_MAX_WEIGHTS; }
+
+} // extern "C"
+
+// the one-workgroup coarse cycle with one omega, or (omegas != NULL) pre weights followed by post weights
+static int coarse_cycle(const gs_stencil* S, const gs_coarse_level* lv, int n, int mode, double omega,
+                        const double* omegas, double gamma, int pre, int post, hipStream_t st)
 {
     mode = base_mode(mode); // (the coarse levels read their factor fields, which hold gamma under GS_NEWTON_G)
     if (!S || !valid_stencil(S) || !lv || n < 1 || n > CC_MAXLEV || mode < GS_LINEAR || mode > GS_NEWTON_B ||
@@ -789,6 +853,9 @@ int gs_coarse_cycle(const gs_stencil* S, const gs_coarse_level* lv, int n, int m
     P.n = n;
     P.pre = pre;
     P.post = post;
+    P.weighted = omegas != nullptr;
+    for (int i = 0; omegas && i < pre; i++) P.wpre[i] = omegas[i];
+    for (int i = 0; omegas && i < post; i++) P.wpost[i] = omegas[pre + i];
     for (int l = 0; l < n; l++) {
         const gs_coarse_level& a = lv[l];
         const gs_level* g = &a.geom;
@@ -821,6 +888,22 @@ int gs_coarse_cycle(const gs_stencil* S, const gs_coarse_level* lv, int n, int m
     else if (mode == GS_NEWTON_B) hipLaunchKernelGGL(k_coarse_cycle<GS_NEWTON_B>, dim3(1), dim3(CC_T), 0, st, P);
     else hipLaunchKernelGGL(k_coarse_cycle<GS_NEWTON>, dim3(1), dim3(CC_T), 0, st, P);
     return launch_status();
+}
+
+extern "C" {
+
+int gs_coarse_cycle(const gs_stencil* S, const gs_coarse_level* lv, int n, int mode, double omega, double gamma,
+                    int pre, int post, hipStream_t st)
+{
+    return coarse_cycle(S, lv, n, mode, omega, nullptr, gamma, pre, post, st);
+}
+
+int gs_coarse_cycle_w(const gs_stencil* S, const gs_coarse_level* lv, int n, int mode, const double* omegas,
+                      double gamma, int pre, int post, hipStream_t st)
+{
+    if (!omegas || pre < 0 || post < 0 || pre > GS_MAX_WEIGHTS || post > GS_MAX_WEIGHTS || pre + post < 1)
+        return GS_EINVAL;
+    return coarse_cycle(S, lv, n, mode, omegas[0], omegas, gamma, pre, post, st);
 }
 
 const char* gs_strerror(int code)

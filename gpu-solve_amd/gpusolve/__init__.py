@@ -20,7 +20,7 @@ from typing import List, Tuple
 import numpy as np
 
 from . import _abi
-from ._abi import GS_LINEAR, GS_NEWTON, GS_NEWTON_B, GS_NEWTON_G, GS_NONLINEAR, gs_level, gs_params, gs_stencil, kernels, driver, diag  # noqa: F401
+from ._abi import GS_LINEAR, GS_MAX_WEIGHTS, GS_NEWTON, GS_NEWTON_B, GS_NEWTON_G, GS_NONLINEAR, gs_level, gs_params, gs_stencil, kernels, driver, diag  # noqa: F401
 
 CANONICAL_OFFSETS = [(0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)]
 
@@ -159,6 +159,29 @@ class HipGridData:
         """The level HipSolver.fmg starts on; 0 when full multigrid is not applicable to this grid."""
         return driver().gs_grid_fmg_start_level(self.handle)
 
+    def set_weights(self, pre, post):
+        """Per-sweep relaxation weights: on every level the k-th pre-smoothing sweep of each V-cycle takes pre[k] and
+        the k-th post-smoothing sweep post[k] instead of omega (the coarsest level: pre, then post). len(pre) /
+        len(post) must equal the grid's preSmoothing / postSmoothing (each at most GS_MAX_WEIGHTS) and every weight
+        be finite, else GpuSolveError and the grid is unchanged. Equal weights give the unweighted solve bit for bit.
+        HipSolver.jacobi (stand-alone sweeps) keeps omega."""
+        pre, post = [float(w) for w in pre], [float(w) for w in post]
+        a, b = (C.c_double * max(1, len(pre)))(*pre), (C.c_double * max(1, len(post)))(*post)
+        _check(driver().gs_grid_set_weights(self.handle, a, len(pre), b, len(post)))
+
+    def clear_weights(self):
+        """Back to the grid's omega for every sweep."""
+        _check(driver().gs_grid_set_weights(self.handle, None, 0, None, 0))
+
+    @property
+    def weights(self):
+        """(pre, post) tuples of the per-sweep weights in force (set_weights or GS_OMEGAS), or None."""
+        npre, npost = int(self.params.preSmoothing), int(self.params.postSmoothing)
+        a, b = (C.c_double * max(1, npre))(), (C.c_double * max(1, npost))()
+        if not driver().gs_grid_get_weights(self.handle, a, b):
+            return None
+        return tuple(a[:npre]), tuple(b[:npost])
+
     def field(self, level: int, name: str) -> np.ndarray:
         """Copy of a padded field as a dense array indexed [x][y][z] (the reference's axis order)."""
         g = self.getLevel(level).geom
@@ -253,6 +276,24 @@ class NewtonSolver:
         if grid.mode != GS_NEWTON:
             raise ValueError("NewtonSolver needs mode NEWTON")
         return HipSolver.solve(grid, print_progress)
+
+
+def chebyshev_weights(nu: int, lo: float = 1.0 / 3.0, hi: float = 2.0) -> Tuple[float, ...]:
+    """The nu Chebyshev relaxation weights on [lo, hi], w_k = 1 / ((hi+lo)/2 + (hi-lo)/2 cos(pi (2k-1) / (2 nu))):
+    prod (1 - w_k x) is the polynomial of least maximum on [lo, hi] among those that are 1 at 0. The default
+    interval is the high-frequency band of D^-1 A for the 7-point operator. Pure host code (no device needed)."""
+    nu = int(nu)
+    out = (C.c_double * max(1, nu))()
+    _check(driver().gs_chebyshev_weights(nu, float(lo), float(hi), out))
+    return tuple(out[:nu])
+
+
+def parse_omegas(text: str, pre: int, post: int) -> Tuple[Tuple[float, ...], Tuple[float, ...]]:
+    """GS_OMEGAS's value ("w1,w2/w3,w4" or "cheb") for a grid of pre / post smoothing sweeps, as (pre, post)
+    weights, with the library's parser; GpuSolveError on a malformed value or a count mismatch. No device needed."""
+    out = (C.c_double * max(1, pre + post))()
+    _check(driver().gs_parse_omegas(text.encode(), int(pre), int(post), out))
+    return tuple(out[:pre]), tuple(out[pre:pre + post])
 
 
 def field_layout(nx: int, ny: int, nz: int):

@@ -19,6 +19,7 @@ GS_LINEAR, GS_NONLINEAR, GS_NEWTON = 0, 1, 2
 GS_NEWTON_B = 3  # NEWTON with the precomputed linearisation factor B (include/gpusolve_hip.h)
 GS_NEWTON_G = 4  # GS_NEWTON_B whose factor field holds gamma everywhere (the first Newton iteration)
 GS_EINVAL = 100001
+GS_MAX_WEIGHTS = 8  # per-sweep relaxation weights per smoothing leg (include/gpusolve_hip.h)
 
 dptr = C.POINTER(C.c_double)
 i64 = C.c_int64
@@ -120,6 +121,30 @@ KERNEL_API = {
     "gs_coarse_cycle_max_levels": (C.c_int, []),
     "gs_coarse_cycle": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_coarse_level), C.c_int, C.c_int, C.c_double,
                                   C.c_double, C.c_int, C.c_int, C.c_void_p]),
+    # the per-sweep-weight siblings (`omegas`: a host array of doubles where the launcher takes omega)
+    "gs_max_weights": (C.c_int, []),
+    "gs_jacobi_sweep2_w": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int, dptr, C.c_double,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "gs_jacobi_sweep2_norm_w": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int, dptr,
+                                          C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_int, C.c_void_p, C.c_void_p]),
+    "gs_jacobi_sweep3_w": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), dptr, C.c_double,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gs_jacobi_sweep2_prolong_w": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int, dptr, C.c_double,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(gs_level), C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "gs_jacobi_sweep2_prolong_ws_w": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int, dptr,
+                                                C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(gs_level),
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, i64,
+                                                C.c_void_p]),
+    "gs_smooth2_restrict_tiled_w": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int, dptr,
+                                              C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(gs_level), C.c_void_p]),
+    "gs_prolong_smooth2_tiled_w": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int, dptr,
+                                             C.c_double, C.c_void_p, C.c_void_p, C.POINTER(gs_level), C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gs_coarse_cycle_w": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_coarse_level), C.c_int, C.c_int, dptr,
+                                    C.c_double, C.c_int, C.c_int, C.c_void_p]),
     "gs_strerror": (C.c_char_p, [C.c_int]),
     "gs_build_info": (C.c_char_p, []),
 }
@@ -133,6 +158,10 @@ DRIVER_API = {
     "gs_grid_vcycle_level": (C.c_int, [C.c_void_p, C.c_int]),
     "gs_grid_fmg": (C.c_int, [C.c_void_p, C.c_int, dptr]),
     "gs_grid_fmg_start_level": (C.c_int, [C.c_void_p]),
+    "gs_grid_set_weights": (C.c_int, [C.c_void_p, dptr, C.c_int, dptr, C.c_int]),
+    "gs_grid_get_weights": (C.c_int, [C.c_void_p, dptr, dptr]),
+    "gs_chebyshev_weights": (C.c_int, [C.c_int, C.c_double, C.c_double, dptr]),
+    "gs_parse_omegas": (C.c_int, [C.c_char_p, C.c_int, C.c_int, dptr]),
     "gs_grid_jacobi": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "gs_grid_residual_norm": (C.c_int, [C.c_void_p, C.c_int, dptr]),
     "gs_grid_num_levels": (C.c_int, [C.c_void_p]),

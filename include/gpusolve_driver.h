@@ -64,6 +64,29 @@ int gs_grid_fmg(void* grid, int cycles_per_level, double* residual);
 /* The level FMG starts on: the deepest level with every transition above it aligned (fine n = 2 coarse n + 1 per
  * axis); 0 when FMG is not applicable to the grid. */
 int gs_grid_fmg_start_level(void* grid);
+/* Per-sweep relaxation weights (added; Chebyshev-Jacobi smoothing). With weights set, on every
+ * level the k-th pre-smoothing sweep of every V-cycle takes pre[k] and the k-th post-smoothing sweep post[k] in place
+ * of the grid's omega; the coarsest level's pre + post sweeps take the pre weights, then the post weights. They apply
+ * to gs_grid_solve in all three modes (NEWTON: its inner V-cycles), gs_grid_vcycle, gs_grid_vcycle_level,
+ * gs_grid_fmg and Z-slab grids, through the same fused launches (the `_w` launchers of gpusolve_hip.h): equal
+ * weights give the unweighted solve bit for bit. npre / npost must equal the grid's pre / post, each at most
+ * GS_MAX_WEIGHTS, every weight finite; (NULL, 0, NULL, 0) clears the weights. On error (return 1) nothing changes
+ * and gs_last_error() holds the reason. gs_grid_jacobi / gs_grid_time_jacobi are stand-alone sweeps and keep omega.
+ * GS_OMEGAS in the environment when the grid is created sets them: "w1,w2/w3,w4" (pre weights, a slash, post
+ * weights) or "cheb" (gs_chebyshev_weights on [1/3, 2] for the grid's own counts); a malformed value or a count
+ * mismatch fails the creation. */
+int gs_grid_set_weights(void* grid, const double* pre, int npre, const double* post, int npost);
+/* 1 and the weights (pre: the grid's pre values, post: its post values; either may be NULL) when weights are set,
+ * else 0. */
+int gs_grid_get_weights(void* grid, double* pre, double* post);
+/* out[k-1] = 1 / ((hi+lo)/2 + (hi-lo)/2 * cos(pi (2k-1) / (2 nu))), k = 1..nu: the weights whose error polynomial
+ * prod (1 - w_k x) is the scaled Chebyshev polynomial of degree nu on [lo, hi]. Pure host code. 1 (and
+ * gs_last_error()) unless nu >= 1 and 0 < lo < hi. */
+int gs_chebyshev_weights(int nu, double lo, double hi, double* out);
+/* GS_OMEGAS's parser on its own (pure host code): the value `text` for a grid of pre / post smoothing sweeps, as
+ * pre + post weights into out (which may be NULL: validation only). 1 (and gs_last_error()) on a malformed value, a
+ * count mismatch, a non-finite weight or more than GS_MAX_WEIGHTS weights per leg. */
+int gs_parse_omegas(const char* text, int pre, int post, double* out);
 int gs_grid_jacobi(void* grid, int level, int sweeps);
 int gs_grid_residual_norm(void* grid, int level, double* norm);
 int gs_grid_num_levels(void* grid);

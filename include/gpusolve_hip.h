@@ -307,6 +307,49 @@ int gs_coarse_cycle_max_levels(void);
 int gs_coarse_cycle(const gs_stencil* S, const gs_coarse_level* lv, int n, int mode, double omega, double gamma,
                     int pre, int post, hipStream_t stream);
 
+/* Per-sweep relaxation weights (added; not a reference feature). Every launcher above that performs more than one
+ * sweep has a sibling `..._w` that takes one weight per sweep as a host array `omegas` (read during the call; the
+ * weights travel by value in the kernel arguments) where the launcher takes the single `omega`: sweep k of the pass
+ * is v + omegas[k] * D^-1 (f - A v), the single sweep's expression with that weight. Everything else — arguments,
+ * supported shapes and modes, zero iterates, workspaces, norm partials (the norm is the input's, so the weights do
+ * not touch it) — is the launcher's own, and a `_w` call with equal weights writes the launcher's words: the
+ * launchers above ARE their siblings called with omega repeated. A NULL `omegas` is GS_EINVAL.
+ *   gs_jacobi_sweep2_w, gs_jacobi_sweep2_norm_w                   2 weights: == gs_jacobi_sweep(omegas[0]) then (omegas[1])
+ *   gs_jacobi_sweep3_w                                            3 weights
+ *   gs_jacobi_sweep2_prolong_w, gs_jacobi_sweep2_prolong_ws_w     2 weights (the two post-smoothing sweeps)
+ *   gs_smooth2_restrict_tiled_w, gs_prolong_smooth2_tiled_w       2 weights
+ *   gs_coarse_cycle_w                                             pre + post weights: omegas[0..pre) are the weights
+ *       of the pre-smoothing sweeps of every level, omegas[pre..pre+post) those of the post-smoothing sweeps; the
+ *       coarsest level's pre + post sweeps (CpuSolver.cpp:117) take the pre weights and then the post weights.
+ *       pre and post are each at most gs_max_weights() (GS_MAX_WEIGHTS) and pre + post >= 1, else GS_EINVAL;
+ *       gs_coarse_cycle itself keeps taking any counts. */
+#define GS_MAX_WEIGHTS 8
+int gs_max_weights(void);
+int gs_jacobi_sweep2_w(const gs_stencil* S, const gs_level* L, int mode, const double* omegas, double gamma,
+                       const double* v_in, double* v_out, const double* f, const double* w, int zlo, int zhi,
+                       hipStream_t stream);
+int gs_jacobi_sweep2_norm_w(const gs_stencil* S, const gs_level* L, int mode, const double* omegas, double gamma,
+                            const double* v_in, double* v_out, const double* f, const double* w, int zlo, int zhi,
+                            double* partials, hipStream_t stream);
+int gs_jacobi_sweep3_w(const gs_stencil* S, const gs_level* L, const double* omegas, double gamma, const double* v_in,
+                       double* v_out, const double* f, hipStream_t stream);
+int gs_jacobi_sweep2_prolong_w(const gs_stencil* S, const gs_level* L, int mode, const double* omegas, double gamma,
+                               const double* v_in, const double* coarse_v, const double* coarse_sub,
+                               const gs_level* coarse, double* v_out, const double* f, const double* w, int zlo,
+                               int zhi, hipStream_t stream);
+int gs_jacobi_sweep2_prolong_ws_w(const gs_stencil* S, const gs_level* L, int mode, const double* omegas, double gamma,
+                                  const double* v_in, const double* coarse_v, const double* coarse_sub,
+                                  const gs_level* coarse, double* v_out, const double* f, const double* w, int zlo,
+                                  int zhi, double* ws, int64_t ws_elems, hipStream_t stream);
+int gs_smooth2_restrict_tiled_w(const gs_stencil* S, const gs_level* fine, int mode, const double* omegas,
+                                double gamma, const double* v_in, double* v_out, const double* f, const double* w,
+                                double* coarse_f, const gs_level* coarse, hipStream_t stream);
+int gs_prolong_smooth2_tiled_w(const gs_stencil* S, const gs_level* fine, int mode, const double* omegas, double gamma,
+                               const double* v_in, const double* coarse_v, const gs_level* coarse, double* v_out,
+                               const double* f, const double* w, hipStream_t stream);
+int gs_coarse_cycle_w(const gs_stencil* S, const gs_coarse_level* lv, int n, int mode, const double* omegas,
+                      double gamma, int pre, int post, hipStream_t stream);
+
 const char* gs_strerror(int code);
 
 /* (tuning variants, bandwidth probes and the rejected k_prr: include/gpusolve_diag.h) */
