@@ -33,6 +33,10 @@
 //   GS_EXP_NODIV  NEWTON's r / den replaced by a multiplication (what the divisions cost)
 //   GS_EXP_EFIELD k_tb2y's NEWTON sweep-1 rows load E = exp(w) from a second field instead of evaluating it
 //                 (the field lies gs_exp_set_efoff(n) elements past newtonV; tools/newton_kprobe.py sets it)
+//   GS_EXP_T3_FLIGHT k_tb3y's sweep 1 takes its z+ operand, row -2 and f from planes already in registers, so no stage
+//                 waits on the newest loads (bounds what more flight time for the loads can buy)
+//   GS_EXP_T3_CHAIN  k_tb3y's sweeps 2 and 3 take their z+ operand from the previous step's plane instead of the stage
+//                 before them (bounds what breaking the stage-to-stage chain can buy)
 // Alternative-arithmetic builds (A/B only; correct results, not the product's choice):
 //   GS_EXP_NB_IEEE   GS_NEWTON_B's Jacobi quotient as the IEEE division instead of nb_quot (r05p)
 #ifdef GS_EXP_NOEXP
@@ -3325,27 +3329,39 @@ bool tbx_pfd2() { return kKnobs.tbxPfd2; }
 
 // The fused triple ("tb3y"): three LINEAR sweeps per pass in k_tb2y's whole-row tile (4 x-waves x 2 mirrored y-waves
 // x TBY_RY rows, one 8-wave block per CU, XCD-aware tile order, z-chunks of tb2_plan). At plane step z a block
-// evaluates sweep 1 at plane z, sweep 2 at plane z-1 and sweep 3 at plane z-2 and stores sweep 3, so a sequence of K
-// sweeps takes K/3 passes over memory instead of K/2. Local rows as in k_tb2y (wave 0: j -> y0-1+j, wave 1 the
-// mirror image y0+2RY-j): own rows j = 1..RY, row RY+1 received from the other y-wave through `yrow` (v(z),
-// sweep-1(z-1), sweep-2(z-2)), rows <= 0 recomputed halo. v is loaded on rows -2..RY (row -2 at plane z only), f on
-// rows -1..RY; sweep 1 is evaluated on rows -1..RY, sweep 2 on rows 0..RY, sweep 3 on rows 1..RY: 9 row evaluations
-// per y-wave and step for 2 output rows. One plane step of prefetch (two operand slots), loads grouped by field,
-// one LDS-only barrier per step, the x-edge columns of every stage through `edge`: each row reads its two edge values
-// where it uses them, straight into the VGPRs the DPP shift takes as its old operand (no readfirstlane, no copy back).
-// State a lane only re-reads itself one or two steps later lives in LDS, not in registers (k_tb2y's wprev_l / fprev_l
-// pattern, no barrier): f of planes z-1 / z-2 for sweeps 2 / 3 and the previous-plane rows of sweeps 1 / 2. With that
+// evaluates sweep 2 at plane z-1, then sweep 3 at plane z-2, which it stores, then sweep 1 at plane z+1, so a sequence
+// of K sweeps takes K/3 passes over memory instead of K/2. Sweep 1 runs one plane ahead of the wavefront and last in
+// the step: it reads only v and f, so the planes loaded at the top of step z-1 are first read after sweeps 2 and 3 of
+// step z (about one and a half steps of flight on the same two operand slots), and its result crosses the step
+// boundary (S1a = sweep 1 at plane z on entry, S1c at z-1, plane z-2 in LDS). Local rows as in k_tb2y (wave 0:
+// j -> y0-1+j, wave 1 the mirror image y0+2RY-j): own rows j = 1..RY, row RY+1 received from the other y-wave through
+// `yrow` (v(z+1), sweep-1(z-1), sweep-2(z-2)), rows <= 0 recomputed halo. v is loaded on rows -2..RY (row -2 at plane
+// z+1 only), f on rows -1..RY; sweep 1 is evaluated on rows -1..RY, sweep 2 on rows 0..RY, sweep 3 on rows 1..RY: 9
+// row evaluations per y-wave and step for 2 output rows. Loads grouped by field, one LDS-only barrier per step, the
+// x-edge columns of every stage through `edge`: each row reads its two edge values where it uses them, straight into
+// the VGPRs the DPP shift takes as its old operand (no readfirstlane, no copy back).
+// State a lane only re-reads itself one or more steps later lives in LDS, not in registers (k_tb2y's wprev_l / fprev_l
+// pattern, no barrier): the previous-plane rows of sweeps 1 / 2 and f. Sweep 1 leaves f(z+1) in the slot of the step's
+// parity, where sweep 2 finds it as f(z-1) two steps later (no copy); sweep 2 hands it on to sweep 3's rows. With that
 // state in registers, or with all the edge values read into VGPRs up front as the LINEAR pair keeps them, every
 // instance spills.
-// A chunk recomputes three prologue steps (z = zb-2 .. zb), whose stage values are formed from whatever the
+// A chunk recomputes four prologue steps (z = zb-3 .. zb), whose stage values are formed from whatever the
 // zero-initialised state gives and are never consumed by a stored value. Boundary rows, columns and planes keep the
 // input value at every stage; plane addresses are clamped to 0..nz+1. Every point goes through the expressions of the
 // one-sweep kernels in the same operand order, so the output is bit-identical to three gs_jacobi_sweep calls.
 // Whole non-distributed levels only (no ghost-plane sides), a real input iterate, no prolongation, no norm partials.
-// DB: the stencil sums of several rows are divided by h^2 in ONE batch (div_hh_mm over two rows of sweep 1, every row
-// of sweeps 2 and 3: four range branches per step instead of nine, and the rows' dependent chains interleave); else
-// row by row. Each quotient is the same value either way. The unit-stencil instances are batched (252 / 256 VGPRs),
-// the general-stencil instance is not (254, its sums through stencil_sum_in_order; batched it spills).
+// DB: the stencil sums of several rows are divided by h^2 in ONE batch (div_hh_mm over two rows of sweep 1 and every
+// row of sweep 2: five range branches per step instead of nine, and the rows' dependent chains interleave); else
+// row by row. Sweep 3 is divided row by row in every instance: it is where the registers peak (both carried sweep-1
+// planes, both sweep-2 planes and both load slots are live), and batched there the unit-stencil instances spill.
+// Each quotient is the same value either way. The unit-stencil instances are batched (254 / 256 VGPRs),
+// the general-stencil instance is not (256, its sums through stencil_sum_in_order).
+// GS_EXP_T3_FLIGHT / GS_EXP_T3_CHAIN: the two timing-only probes of the step's shape (top of this file).
+#ifdef GS_EXP_T3_CHAIN
+#define GS_T3_ZP(n, c) c
+#else
+#define GS_T3_ZP(n, c) n
+#endif
 template <bool UN, bool FX, bool DB>
 __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double* __restrict__ v,
                                                            const double* __restrict__ f, double* __restrict__ out,
@@ -3356,14 +3372,15 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
     constexpr int N0 = RY + 2;       // v, f, sweep-1 rows j = -1..RY at index j+1
     constexpr int N1 = RY + 1;       // sweep-2 rows j = 0..RY at index j
     constexpr int NE = N0 + N1 + RY; // x-edge values per wave side: v rows -1..RY, sweep-1 rows 0..RY, sweep-2 rows 1..RY
-    constexpr int B1 = DB ? 2 : 1, B2 = DB ? N1 : 1, B3 = DB ? RY : 1; // rows per division batch of sweeps 1, 2, 3
+    constexpr int B1 = DB ? 2 : 1, B2 = DB ? N1 : 1, B3 = 1; // rows per division batch of sweeps 1, 2, 3
     // x-edges: [parity][y-wave][1 + x-wave][side][value]; x-wave slots 0 and WX+1 are the zero x-boundary columns
     __shared__ double edge[2][2][WXMAX + 2][2][NE];
     // y-edge rows: [parity][y-wave][x-wave][v | sweep-1 | sweep-2][lane]
     __shared__ double2 yrow[2][2][WXMAX][3][WAVE];
-    // per-lane state, [row][wave][lane]: f at planes z-1 (rows 0..RY) and z-2 (rows 1..RY), sweep 1 at plane z-2
+    // per-lane state, [row][wave][lane]: f at planes z-1 / z (rows 0..RY) and z-2 (rows 1..RY), sweep 1 at plane z-2
     // (rows 0..RY), sweep 2 at plane z-3 (rows 1..RY)
-    __shared__ double2 f1_l[N1][2 * WXMAX][WAVE];
+    // (f1_l: two slots by step parity; sweep 1 writes f(z+1) into the slot sweep 2 reads two steps later)
+    __shared__ double2 f1_l[2][N1][2 * WXMAX][WAVE];
     __shared__ double2 f2_l[RY][2 * WXMAX][WAVE];
     __shared__ double2 s1p_l[N1][2 * WXMAX][WAVE];
     __shared__ double2 s2p_l[RY][2 * WXMAX][WAVE];
@@ -3400,14 +3417,14 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
     auto cz = [&](int z) { return min(max(z, 0), nz + 1); }; // planes below 0 / above nz+1 are never dereferenced
     auto at = [&](const double* base, int j, int z) { return base + xl + roff[j + 2] + (int64_t)z * ldz; };
 
-    double2 Vp[N0], Vc[N0], VL[2][N0], FL[2][N0], HL[2]; // v(z-1), v(z); per slot: v(z+1), f(z), v(z) at row -2
-    double2 S1c[N0], S2c[N1];                            // sweep 1 at plane z-1, sweep 2 at plane z-2
+    double2 Vp[N0], Vc[N0], VL[2][N0], FL[2][N0], HL[2]; // v(z), v(z+1); per slot: v(z+2), f(z+1), v(z+1) at row -2
+    double2 S1a[N0], S1c[N0], S2c[N1];                   // sweep 1 at planes z and z-1, sweep 2 at plane z-2
 #pragma unroll
-    for (int i = 0; i < N0; i++) S1c[i] = make_double2(0.0, 0.0);
+    for (int i = 0; i < N0; i++) S1a[i] = S1c[i] = make_double2(0.0, 0.0);
 #pragma unroll
     for (int i = 0; i < N1; i++) {
         S2c[i] = make_double2(0.0, 0.0);
-        f1_l[i][wid][lane] = make_double2(0.0, 0.0);
+        f1_l[0][i][wid][lane] = f1_l[1][i][wid][lane] = make_double2(0.0, 0.0);
         s1p_l[i][wid][lane] = make_double2(0.0, 0.0);
     }
 #pragma unroll
@@ -3429,12 +3446,12 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
         Vc[i] = ld2(at(v, i - 1, cz(zb - 2)));
     }
     load_slot(1, cz(zb - 2), cz(zb - 1));
-    for (int z0 = zb - 2; z0 <= ze + 2; z0 += 2) {
+    for (int z0 = zb - 3; z0 <= ze + 2; z0 += 2) {
 #pragma unroll
         for (int ph = 0; ph < 2; ph++) {
             const int z = z0 + ph; // (a step past ze+2 loads clamped planes and stores nothing)
             const int cs = ph ^ 1; // slot holding this step's operands
-            load_slot(ph, cz(z + 1), cz(z + 2));
+            load_slot(ph, cz(z + 2), cz(z + 3));
             // ---- publish: x-edge columns of the three stages and the y-edge rows
             if (lane == 0) {
 #pragma unroll
@@ -3492,35 +3509,48 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
             };
             // ---- the three sweeps; wave 1 (mirrored rows) runs its own copy of the code. The keep selects run only
             // where some row, column or the plane is a boundary (a wave-uniform branch)
-            double2 S1n[N0], S2n[N1], F1[N1]; // F1: f at plane z-1 as sweep 2 read it (-> f2_l)
-            const bool pz0 = planeok(z), pz1 = planeok(z - 1);
-            auto sweeps = [&](auto mirc) {
-                // sweep 1 at plane z, local rows -1..RY
-                static_assert(N0 % B1 == 0 && N1 % B2 == 0 && RY % B3 == 0, "whole division batches");
+            // sweep 1 at plane z+1, sweep 2 at plane z-1; F1: f at plane z-1 as sweep 2 read it (-> f2_l)
+            double2 S1n[N0], S2n[N1], F1[N1];
+            const bool pz0 = planeok(z + 1), pz1 = planeok(z - 1);
+            static_assert(N0 % B1 == 0 && N1 % B2 == 0 && RY % B3 == 0, "whole division batches");
+            // sweep 1 at plane z+1, local rows -1..RY
+            auto sweep1 = [&](auto mirc) {
 #pragma unroll
                 for (int b = 0; b < N0; b += B1) {
                     double q[2 * B1];
 #pragma unroll
                     for (int i = b; i < b + B1; i++)
+#ifdef GS_EXP_T3_FLIGHT
+                        row_sums(mirc, Vc[i], i == 0 ? Vc[1] : Vc[i - 1], i == N0 - 1 ? vY : Vc[i + 1], Vp[i], Vp[i],
+                                 CL[i], CR[i], q[2 * (i - b)], q[2 * (i - b) + 1]);
+#else
                         row_sums(mirc, Vc[i], i == 0 ? HL[cs] : Vc[i - 1], i == N0 - 1 ? vY : Vc[i + 1], Vp[i], VL[cs][i],
                                  CL[i], CR[i], q[2 * (i - b)], q[2 * (i - b) + 1]);
+#endif
                     div_hh_mm(k, q);
 #pragma unroll
                     for (int i = b; i < b + B1; i++)
+#ifdef GS_EXP_T3_FLIGHT
+                        S1n[i] = row_finish(k.omega[0], Vc[i], q[2 * (i - b)], q[2 * (i - b) + 1], Vp[i]);
+#else
                         S1n[i] = row_finish(k.omega[0], Vc[i], q[2 * (i - b)], q[2 * (i - b) + 1], FL[cs][i]);
+#endif
                 }
                 if (!FX || !pz0 || !in1) {
 #pragma unroll
                     for (int i = 0; i < N0; i++) S1n[i] = kept(!pz0 || !rowc[i + 1], Vc[i], S1n[i]);
                 }
-                // sweep 2 at plane z-1, local rows 0..RY
+            };
+            // sweep 2 at plane z-1, local rows 0..RY
+            auto sweep2 = [&](auto mirc) {
 #pragma unroll
                 for (int b = 0; b < N1; b += B2) {
                     double q[2 * B2];
 #pragma unroll
                     for (int i = b; i < b + B2; i++) {
-                        F1[i] = f1_l[i][wid][lane];
-                        row_sums(mirc, S1c[i + 1], S1c[i], i == N1 - 1 ? s1Y : S1c[i + 2], s1p_l[i][wid][lane], S1n[i + 1],
+                        F1[i] = f1_l[ph][i][wid][lane];
+                        row_sums(mirc, S1c[i + 1], S1c[i], i == N1 - 1 ? s1Y : S1c[i + 2], s1p_l[i][wid][lane],
+                                 GS_T3_ZP(S1a[i + 1], S1c[i + 1]),
                                  CL[N0 + i], CR[N0 + i], q[2 * (i - b)], q[2 * (i - b) + 1]);
                     }
                     div_hh_mm(k, q);
@@ -3532,7 +3562,9 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
 #pragma unroll
                     for (int i = 0; i < N1; i++) S2n[i] = kept(!pz1 || !rowc[i + 2], S1c[i + 1], S2n[i]);
                 }
-                // sweep 3 at plane z-2, own rows 1..RY
+            };
+            // sweep 3 at plane z-2, own rows 1..RY
+            auto sweep3 = [&](auto mirc) {
                 if (z - 2 >= zb && z - 2 <= ze) {
                     const int64_t zo = (int64_t)(z - 2) * ldz;
 #pragma unroll
@@ -3542,8 +3574,9 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
 #pragma unroll
                         for (int j = b; j < b + B3; j++) {
                             fv[j - b] = f2_l[j - 1][wid][lane];
-                            row_sums(mirc, S2c[j], S2c[j - 1], j == RY ? s2Y : S2c[j + 1], s2p_l[j - 1][wid][lane], S2n[j],
-                                     CL[N0 + N1 + j - 1], CR[N0 + N1 + j - 1], q[2 * (j - b)], q[2 * (j - b) + 1]);
+                            row_sums(mirc, S2c[j], S2c[j - 1], j == RY ? s2Y : S2c[j + 1], s2p_l[j - 1][wid][lane],
+                                     GS_T3_ZP(S2n[j], S2c[j]), CL[N0 + N1 + j - 1], CR[N0 + N1 + j - 1], q[2 * (j - b)],
+                                     q[2 * (j - b) + 1]);
                         }
                         div_hh_mm(k, q);
 #pragma unroll
@@ -3558,9 +3591,9 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
                     }
                 }
             };
-            if (mir) sweeps(BoolC<true>{});
-            else sweeps(BoolC<false>{});
-            // ---- rotate (each lane's LDS rows were read above by this lane alone) ----
+            if (mir) sweep2(BoolC<true>{}), sweep3(BoolC<true>{});
+            else sweep2(BoolC<false>{}), sweep3(BoolC<false>{});
+            // ---- rotate the state of sweeps 2 and 3 (each lane's LDS rows are read by this lane alone) ...
 #pragma unroll
             for (int j = 1; j <= RY; j++) {
                 s2p_l[j - 1][wid][lane] = S2c[j];
@@ -3570,11 +3603,17 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
             for (int i = 0; i < N1; i++) {
                 S2c[i] = S2n[i];
                 s1p_l[i][wid][lane] = S1c[i + 1];
-                f1_l[i][wid][lane] = FL[cs][i + 1];
             }
 #pragma unroll
+            for (int i = 0; i < N0; i++) S1c[i] = S1a[i];
+            // ---- ... then sweep 1, which reads only v and f: the second, independent chain of the step
+            if (mir) sweep1(BoolC<true>{});
+            else sweep1(BoolC<false>{});
+#pragma unroll
+            for (int i = 0; i < N1; i++) f1_l[ph][i][wid][lane] = FL[cs][i + 1];
+#pragma unroll
             for (int i = 0; i < N0; i++) {
-                S1c[i] = S1n[i];
+                S1a[i] = S1n[i];
                 Vp[i] = Vc[i];
                 Vc[i] = VL[cs][i];
             }

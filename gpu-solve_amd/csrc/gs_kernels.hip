@@ -915,7 +915,8 @@ const char* gs_strerror(int code)
 
 const char* gs_build_info(void)
 {
-    return "gpusolve_hip v15: LINEAR triples k_tb3y(the pair's whole-row tile, three sweeps per pass, one-step prefetch, "
+    return "gpusolve_hip v16: LINEAR triples k_tb3y(the pair's whole-row tile, three sweeps per pass, sweep 1 one plane "
+           "ahead and last in the step, two load slots, "
            "per-lane f / previous-plane rows in LDS, x-edge values read row by row from LDS into the DPP shift), "
            "pairs k_tb2y(4x2 waves, 2 rows/wave, one round of z-chunks on large levels, LINEAR 2-step prefetch; +prolong; "
            "512-point column blocks for longer rows in every mode; from 64^3 levels; zero-iterate chunks fitted to "
