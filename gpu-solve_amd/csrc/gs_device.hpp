@@ -141,11 +141,12 @@ bool valid_stencil(const gs_stencil* S)
 //   GS_RR_NG=2           k_rr2 with two groups of coarse rows per block (default 1: measured faster, r05b)
 //   GS_PAIR_FX=0         LINEAR plain pairs always through the instance with per-lane range selects (A/B, r06)
 //   GS_FMG_NT=0|1        gs_fmg_prolong's fine stores never / always non-temporal (default: from 2^25 fine points) (A/B)
+//   GS_T3_SADDR=0        the fused triple's unit-stencil instances with per-lane 64-bit addresses (A/B)
 struct Knobs {
     bool unitStencil, tbxPfd2, pairXh, fitRounds, bigChunks, oneRound, rrLds, zeroQ, newtonXh, specCached;
     int xhSwizzle, midZc, rrZc, rrZcBig, oneRoundMid, rbZc;
     int slabZc, pairZc, rrNr, rrNtu, rrReverse, rrNg, rrDma;
-    bool pairFx;
+    bool pairFx, t3Saddr;
     int fmgNt;
     int64_t pairMinBlocks;
     static int num(const char* name, int dflt)
@@ -161,7 +162,7 @@ struct Knobs {
           newtonXh(num("GS_NEWTON_XH", 1) != 0), specCached(num("GS_SPEC_CACHED", 0) != 0),
           xhSwizzle(num("GS_XH_SWIZZLE", 1)), midZc(num("GS_MID_ZC", 0)), rrZc(num("GS_RR_ZC", 0)), rrZcBig(num("GS_RR_ZC_BIG", 0)), oneRoundMid(num("GS_PAIR_ONE_ROUND_MID", 0)), rbZc(num("GS_RB_ZC", 0)), slabZc(num("GS_SLAB_ZC", 0)), pairZc(num("GS_PAIR_ZC", 0)),
           rrNr(num("GS_RR_NR", 0)), rrNtu(num("GS_RR_NTU", 2)), rrReverse(num("GS_RR_REVERSE", 1)), rrNg(num("GS_RR_NG", 0)), rrDma(num("GS_RR_DMA", 0)),
-          pairFx(num("GS_PAIR_FX", 1) != 0), fmgNt(num("GS_FMG_NT", -1)),
+          pairFx(num("GS_PAIR_FX", 1) != 0), t3Saddr(num("GS_T3_SADDR", 1) != 0), fmgNt(num("GS_FMG_NT", -1)),
           pairMinBlocks(num("GS_PAIR_MIN_BLOCKS", 128))
     {
     }
@@ -574,6 +575,41 @@ __device__ __forceinline__ void st2s(double* __restrict__ p, double a, double b)
         *reinterpret_cast<double2*>(p) = make_double2(a, b);
     }
 }
+
+// Scalar-base addressing (k_tb3y): a wave-uniform 64-bit byte address held in SGPRs plus one 32-bit lane offset, the
+// `global_load_dwordx4 v, v_off, s[base:base+1]` form, so that no lane keeps a 64-bit address. Two things keep the
+// compiler from undoing it. (1) The uniform base goes through an empty asm statement with an SGPR constraint: without it
+// base + row + lane offset is reassociated, the loop-invariant part (row + lane offset) hoisted into a 64-bit VGPR pair
+// per row, and the plane offset added per step with v_lshl_add_u64. The INTEGER is laundered and then cast to a
+// global (address_space(1)) pointer: laundering a pointer loses its address space and gives flat_load. (2) The lane
+// offset stays a 32-bit value that is redefined in the loop (sa_lane, once per plane step), so its zero-extension is
+// formed where the access is selected; hoisted out of the loop it is a 64-bit VGPR again and selection falls back to
+// v_lshl_add_u64 plus `off`. Neither statement emits an instruction (not volatile: the scheduler moves them freely).
+typedef __attribute__((address_space(1))) const dv2 sa_cdv2;
+typedef __attribute__((address_space(1))) dv2 sa_dv2;
+typedef __attribute__((address_space(1))) double sa_d;
+__device__ __forceinline__ uint64_t sa_base(const double* p)
+{
+    uint64_t a = reinterpret_cast<uint64_t>(p);
+    asm("" : "+s"(a));
+    return a;
+}
+__device__ __forceinline__ unsigned sa_lane(unsigned off)
+{
+    asm("" : "+v"(off));
+    return off;
+}
+__device__ __forceinline__ double2 sa_ld2(uint64_t base, unsigned off)
+{
+    const dv2 t = *reinterpret_cast<sa_cdv2*>(base + off);
+    return make_double2(t.x, t.y);
+}
+__device__ __forceinline__ void sa_st2nt(uint64_t base, unsigned off, double a, double b)
+{
+    const dv2 t = {a, b};
+    __builtin_nontemporal_store(t, reinterpret_cast<sa_dv2*>(base + off));
+}
+__device__ __forceinline__ void sa_st1(uint64_t base, unsigned off, double a) { *reinterpret_cast<sa_d*>(base + off) = a; }
 
 // Loads of the iterate; ZV: the iterate is identically zero (a coarse level's first sweep after
 // the reference's v = 0) and is not read at all. Multiplying the literal zeros keeps the arithmetic,
@@ -3344,25 +3380,31 @@ bool tbx_pfd2() { return kKnobs.tbxPfd2; }
 // pattern, no barrier): the previous-plane rows of sweeps 1 / 2 and f. Sweep 1 leaves f(z+1) in the slot of the step's
 // parity, where sweep 2 finds it as f(z-1) two steps later (no copy); sweep 2 hands it on to sweep 3's rows. With that
 // state in registers, or with all the edge values read into VGPRs up front as the LINEAR pair keeps them, every
-// instance spills.
+// instance with per-lane addresses spills.
+// SA: every load and store as a wave-uniform row base on the scalar unit plus one 32-bit lane offset (sa_base above):
+// no lane holds a 64-bit address, which gives 20 VGPRs back. They hold the previous-plane rows of sweeps 1 and 2 and
+// sweep 3's f (S1p, S2p, F2: 7 LDS writes and 7 LDS reads of 16 B per lane and step less; f1_l stays in LDS), and
+// sweep 1 is divided in one batch of its four rows. The unit-stencil instances (246 / 252 VGPRs); the general-stencil
+// instance would spill 13 SGPRs to VGPR lanes and keeps SA = false, which is also what GS_T3_SADDR=0 selects (A/B).
 // A chunk recomputes four prologue steps (z = zb-3 .. zb), whose stage values are formed from whatever the
 // zero-initialised state gives and are never consumed by a stored value. Boundary rows, columns and planes keep the
 // input value at every stage; plane addresses are clamped to 0..nz+1. Every point goes through the expressions of the
 // one-sweep kernels in the same operand order, so the output is bit-identical to three gs_jacobi_sweep calls.
 // Whole non-distributed levels only (no ghost-plane sides), a real input iterate, no prolongation, no norm partials.
-// DB: the stencil sums of several rows are divided by h^2 in ONE batch (div_hh_mm over two rows of sweep 1 and every
-// row of sweep 2: five range branches per step instead of nine, and the rows' dependent chains interleave); else
-// row by row. Sweep 3 is divided row by row in every instance: it is where the registers peak (both carried sweep-1
+// DB: the stencil sums of several rows are divided by h^2 in ONE batch (div_hh_mm over two rows of sweep 1, all four
+// with SA, and every row of sweep 2: five (four) range branches per step instead of nine, and the rows' dependent
+// chains interleave); else row by row.
+// Sweep 3 is divided row by row in every instance: it is where the registers peak (both carried sweep-1
 // planes, both sweep-2 planes and both load slots are live), and batched there the unit-stencil instances spill.
-// Each quotient is the same value either way. The unit-stencil instances are batched (254 / 256 VGPRs),
-// the general-stencil instance is not (256, its sums through stencil_sum_in_order).
+// Each quotient is the same value either way. The unit-stencil instances are batched (254 / 256 VGPRs with per-lane
+// addresses), the general-stencil instance is not (256, its sums through stencil_sum_in_order).
 // GS_EXP_T3_FLIGHT / GS_EXP_T3_CHAIN: the two timing-only probes of the step's shape (top of this file).
 #ifdef GS_EXP_T3_CHAIN
 #define GS_T3_ZP(n, c) c
 #else
 #define GS_T3_ZP(n, c) n
 #endif
-template <bool UN, bool FX, bool DB>
+template <bool UN, bool FX, bool DB, bool SA>
 __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double* __restrict__ v,
                                                            const double* __restrict__ f, double* __restrict__ out,
                                                            int nx, int ny, int nz, int64_t ldy, int64_t ldz, int ZC)
@@ -3372,7 +3414,8 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
     constexpr int N0 = RY + 2;       // v, f, sweep-1 rows j = -1..RY at index j+1
     constexpr int N1 = RY + 1;       // sweep-2 rows j = 0..RY at index j
     constexpr int NE = N0 + N1 + RY; // x-edge values per wave side: v rows -1..RY, sweep-1 rows 0..RY, sweep-2 rows 1..RY
-    constexpr int B1 = DB ? 2 : 1, B2 = DB ? N1 : 1, B3 = 1; // rows per division batch of sweeps 1, 2, 3
+    constexpr int B1 = DB ? (SA ? N0 : 2) : 1, B2 = DB ? N1 : 1, B3 = 1; // rows per division batch of sweeps 1, 2, 3
+    constexpr bool RS = SA; // the previous-plane rows of sweeps 1 / 2 and sweep 3's f in registers, not in LDS
     // x-edges: [parity][y-wave][1 + x-wave][side][value]; x-wave slots 0 and WX+1 are the zero x-boundary columns
     __shared__ double edge[2][2][WXMAX + 2][2][NE];
     // y-edge rows: [parity][y-wave][x-wave][v | sweep-1 | sweep-2][lane]
@@ -3416,34 +3459,47 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
     auto planeok = [&](int z) { return z >= 1 && z <= nz; };
     auto cz = [&](int z) { return min(max(z, 0), nz + 1); }; // planes below 0 / above nz+1 are never dereferenced
     auto at = [&](const double* base, int j, int z) { return base + xl + roff[j + 2] + (int64_t)z * ldz; };
+    // SA: the row's base on the scalar unit, the lane's byte offset in one VGPR (sa_base above). A lane that stores
+    // has x <= nx, so xl == x there and the stores take the loads' offset.
+    unsigned xo = 8u * (unsigned)xl;
+    auto ldrow = [&](const double* base, int j, int z) {
+        if constexpr (SA) return sa_ld2(sa_base(base + roff[j + 2] + (int64_t)z * ldz), xo);
+        else return ld2(at(base, j, z));
+    };
 
     double2 Vp[N0], Vc[N0], VL[2][N0], FL[2][N0], HL[2]; // v(z), v(z+1); per slot: v(z+2), f(z+1), v(z+1) at row -2
     double2 S1a[N0], S1c[N0], S2c[N1];                   // sweep 1 at planes z and z-1, sweep 2 at plane z-2
+    double2 S1p[N1], S2p[RY], F2[RY];                    // RS: sweep 1 at plane z-2, sweep 2 at plane z-3, f at plane z-2
 #pragma unroll
     for (int i = 0; i < N0; i++) S1a[i] = S1c[i] = make_double2(0.0, 0.0);
 #pragma unroll
     for (int i = 0; i < N1; i++) {
         S2c[i] = make_double2(0.0, 0.0);
         f1_l[0][i][wid][lane] = f1_l[1][i][wid][lane] = make_double2(0.0, 0.0);
-        s1p_l[i][wid][lane] = make_double2(0.0, 0.0);
+        if constexpr (RS) S1p[i] = make_double2(0.0, 0.0);
+        else s1p_l[i][wid][lane] = make_double2(0.0, 0.0);
     }
 #pragma unroll
     for (int i = 0; i < RY; i++) {
-        f2_l[i][wid][lane] = make_double2(0.0, 0.0);
-        s2p_l[i][wid][lane] = make_double2(0.0, 0.0);
+        if constexpr (RS) {
+            S2p[i] = F2[i] = make_double2(0.0, 0.0);
+        } else {
+            f2_l[i][wid][lane] = make_double2(0.0, 0.0);
+            s2p_l[i][wid][lane] = make_double2(0.0, 0.0);
+        }
     }
     // a step's loads grouped by field, rows ascending (as the LINEAR plain pair, GRP)
     auto load_slot = [&](const int s, const int z, const int zv) {
-        HL[s] = ld2(at(v, -2, z));
+        HL[s] = ldrow(v, -2, z);
 #pragma unroll
-        for (int i = 0; i < N0; i++) VL[s][i] = ld2(at(v, i - 1, zv));
+        for (int i = 0; i < N0; i++) VL[s][i] = ldrow(v, i - 1, zv);
 #pragma unroll
-        for (int i = 0; i < N0; i++) FL[s][i] = ld2(at(f, i - 1, z));
+        for (int i = 0; i < N0; i++) FL[s][i] = ldrow(f, i - 1, z);
     };
 #pragma unroll
     for (int i = 0; i < N0; i++) {
-        Vp[i] = ld2(at(v, i - 1, cz(zb - 3)));
-        Vc[i] = ld2(at(v, i - 1, cz(zb - 2)));
+        Vp[i] = ldrow(v, i - 1, cz(zb - 3));
+        Vc[i] = ldrow(v, i - 1, cz(zb - 2));
     }
     load_slot(1, cz(zb - 2), cz(zb - 1));
     for (int z0 = zb - 3; z0 <= ze + 2; z0 += 2) {
@@ -3451,6 +3507,7 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
         for (int ph = 0; ph < 2; ph++) {
             const int z = z0 + ph; // (a step past ze+2 loads clamped planes and stores nothing)
             const int cs = ph ^ 1; // slot holding this step's operands
+            if constexpr (SA) xo = sa_lane(xo);
             load_slot(ph, cz(z + 2), cz(z + 3));
             // ---- publish: x-edge columns of the three stages and the y-edge rows
             if (lane == 0) {
@@ -3549,7 +3606,8 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
 #pragma unroll
                     for (int i = b; i < b + B2; i++) {
                         F1[i] = f1_l[ph][i][wid][lane];
-                        row_sums(mirc, S1c[i + 1], S1c[i], i == N1 - 1 ? s1Y : S1c[i + 2], s1p_l[i][wid][lane],
+                        row_sums(mirc, S1c[i + 1], S1c[i], i == N1 - 1 ? s1Y : S1c[i + 2],
+                                 RS ? S1p[i] : s1p_l[i][wid][lane],
                                  GS_T3_ZP(S1a[i + 1], S1c[i + 1]),
                                  CL[N0 + i], CR[N0 + i], q[2 * (i - b)], q[2 * (i - b) + 1]);
                     }
@@ -3573,8 +3631,9 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
                         double2 fv[B3];
 #pragma unroll
                         for (int j = b; j < b + B3; j++) {
-                            fv[j - b] = f2_l[j - 1][wid][lane];
-                            row_sums(mirc, S2c[j], S2c[j - 1], j == RY ? s2Y : S2c[j + 1], s2p_l[j - 1][wid][lane],
+                            fv[j - b] = RS ? F2[j - 1] : f2_l[j - 1][wid][lane];
+                            row_sums(mirc, S2c[j], S2c[j - 1], j == RY ? s2Y : S2c[j + 1],
+                                     RS ? S2p[j - 1] : s2p_l[j - 1][wid][lane],
                                      GS_T3_ZP(S2n[j], S2c[j]), CL[N0 + N1 + j - 1], CR[N0 + N1 + j - 1], q[2 * (j - b)],
                                      q[2 * (j - b) + 1]);
                         }
@@ -3583,9 +3642,16 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
                         for (int j = b; j < b + B3; j++) {
                             const double2 o = row_finish(k.omega[2], S2c[j], q[2 * (j - b)], q[2 * (j - b) + 1], fv[j - b]);
                             if (yof(j) <= ny) {
-                                double* qo = out + x + roff[j + 2] + zo;
-                                if (okx1) st2s<true>(qo, o.x, o.y);
-                                else if (okx0) *qo = o.x;
+                                if constexpr (SA) {
+                                    xo = sa_lane(xo); // (redefined in the store's own block: sa_base above)
+                                    const uint64_t qb = sa_base(out + roff[j + 2] + zo);
+                                    if (okx1) sa_st2nt(qb, xo, o.x, o.y);
+                                    else if (okx0) sa_st1(qb, xo, o.x);
+                                } else {
+                                    double* qo = out + x + roff[j + 2] + zo;
+                                    if (okx1) st2s<true>(qo, o.x, o.y);
+                                    else if (okx0) *qo = o.x;
+                                }
                             }
                         }
                     }
@@ -3596,13 +3662,19 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
             // ---- rotate the state of sweeps 2 and 3 (each lane's LDS rows are read by this lane alone) ...
 #pragma unroll
             for (int j = 1; j <= RY; j++) {
-                s2p_l[j - 1][wid][lane] = S2c[j];
-                f2_l[j - 1][wid][lane] = F1[j];
+                if constexpr (RS) {
+                    S2p[j - 1] = S2c[j];
+                    F2[j - 1] = F1[j];
+                } else {
+                    s2p_l[j - 1][wid][lane] = S2c[j];
+                    f2_l[j - 1][wid][lane] = F1[j];
+                }
             }
 #pragma unroll
             for (int i = 0; i < N1; i++) {
                 S2c[i] = S2n[i];
-                s1p_l[i][wid][lane] = S1c[i + 1];
+                if constexpr (RS) S1p[i] = S1c[i + 1];
+                else s1p_l[i][wid][lane] = S1c[i + 1];
             }
 #pragma unroll
             for (int i = 0; i < N0; i++) S1c[i] = S1a[i];

@@ -231,11 +231,20 @@ int gs_jacobi_sweep3_w(const gs_stencil* S, const gs_level* L, const double* ome
         return GS_EINVAL;
     const Coef k = make_coef_w(S, L, omegas, 3, gamma);
     const int nx = (int)L->nx, ny = (int)L->ny, nz = (int)L->nz;
-#define GS_TB3(U, X) hipLaunchKernelGGL((k_tb3y<U, X, U>), g, b, 0, st, k, v_in, f, v_out, nx, ny, nz, L->ldy, L->ldz, zc)
-    // FX: rows of whole 128-point waves, as the pair's (GS_PAIR_FX=0: the general instance)
-    if (k.unit && kKnobs.pairFx && nx % (2 * WAVE) == 0) GS_TB3(true, true);
-    else if (k.unit) GS_TB3(true, false);
-    else GS_TB3(false, false);
+#define GS_TB3(U, X, A)                                                                                                \
+    hipLaunchKernelGGL((k_tb3y<U, X, U, A>), g, b, 0, st, k, v_in, f, v_out, nx, ny, nz, L->ldy, L->ldz, zc)
+#define GS_TB3A(U, X)                                                                                                  \
+    do {                                                                                                               \
+        if (kKnobs.t3Saddr) GS_TB3(U, X, true);                                                                        \
+        else GS_TB3(U, X, false);                                                                                      \
+    } while (0)
+    // FX: rows of whole 128-point waves, as the pair's (GS_PAIR_FX=0: the general instance). The unit-stencil instances
+    // address through scalar row bases (GS_T3_SADDR=0: per-lane 64-bit addresses, A/B); the general-stencil instance
+    // keeps the per-lane addresses, with scalar bases it spills 13 SGPRs to VGPR lanes
+    if (k.unit && kKnobs.pairFx && nx % (2 * WAVE) == 0) GS_TB3A(true, true);
+    else if (k.unit) GS_TB3A(true, false);
+    else GS_TB3(false, false, false);
+#undef GS_TB3A
 #undef GS_TB3
     return launch_status();
 }
@@ -915,9 +924,10 @@ const char* gs_strerror(int code)
 
 const char* gs_build_info(void)
 {
-    return "gpusolve_hip v16: LINEAR triples k_tb3y(the pair's whole-row tile, three sweeps per pass, sweep 1 one plane "
-           "ahead and last in the step, two load slots, "
-           "per-lane f / previous-plane rows in LDS, x-edge values read row by row from LDS into the DPP shift), "
+    return "gpusolve_hip v17: LINEAR triples k_tb3y(the pair's whole-row tile, three sweeps per pass, sweep 1 one plane "
+           "ahead and last in the step, two load slots, scalar row bases + 32-bit lane offsets, "
+           "previous-plane rows in registers, per-lane f in LDS, x-edge values read row by row from LDS into the DPP "
+           "shift), "
            "pairs k_tb2y(4x2 waves, 2 rows/wave, one round of z-chunks on large levels, LINEAR 2-step prefetch; +prolong; "
            "512-point column blocks for longer rows in every mode; from 64^3 levels; zero-iterate chunks fitted to "
            "resident rounds; zero iterates q = +0; whole-wave rows without range selects (FX); LINEAR loads grouped by "
