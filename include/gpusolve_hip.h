@@ -27,9 +27,31 @@
  *    (x,y,z), 0 <= x <= nx+1 etc., lives at ptr[x + y*ldy + z*ldz]  (x unit-stride, z slowest;
  *    the reference's (x,y,z) semantics, not its z-fastest storage). `ptr` is the address of
  *    padded element (0,0,0). gs_field_layout() gives the pitches and an allocation recipe that
- *    makes every interior x=1 element 128-byte aligned (speed only; any pitch >= nx+2 is correct)
+ *    makes every interior x=1 element 128-byte aligned (speed only, see the layout contract below)
  *    and provides planes z = -1 and z = nz+2 (the second ghost plane of a Z-slab, read only by the
  *    fused two-sweep launcher gs_jacobi_sweep2 when a slab side is an internal boundary).
+ *  - Layout contract (tests/test_gpu_layouts.py runs every launcher below under it, in five layouts):
+ *    * Accepted: every ldy >= nx+2 and ldz >= ldy*(ny+2), odd pitches included, and every field pointer that is
+ *      8-byte aligned; the operands of one call may sit at different 16-byte phases. Smaller pitches are
+ *      GS_EINVAL and nothing is written. Nothing else about pitch or alignment changes a result: the kernels'
+ *      16-byte pair accesses are then issued at addresses that are 8 mod 16, which the device serves (global
+ *      memory's unaligned access mode, ROCm's default).
+ *    * Results depend only on the padded box (x, y, z) in [0, nx+1] x [0, ny+1] x [0, nz+1] of each input, plus
+ *      the ghost planes a launcher names for zlo / zhi (and, for gs_newton_bfac, all of planes -1 .. nz+2). Pitch
+ *      padding, the gap between planes, ghost planes not named and memory around the field may hold anything,
+ *      NaNs included. Of f, w (newtonV or the GS_NEWTON_B factor) and F only interior points take part, and the
+ *      boundary planes 0 / nz+1 of an internal slab side; their ring may hold anything. The ring of v / e / restV
+ *      must hold 0 (below).
+ *    * Written: exactly the set each launcher documents — the interior of its outputs unless it says otherwise
+ *      (the whole padded box: gs_interpolate, gs_rhs_init outside LINEAR mode; planes -1 .. nz+2 at full pitch:
+ *      gs_newton_bfac; n partials, ws_elems workspace doubles). Inputs are not written.
+ *    * Readable extent. The kernels load with clamped indices and in pairs, so they READ (without using) words
+ *      outside the box: of any field, planes -1 .. nz+2 (index clamps of the z-marches), rows 0 .. ny+1, columns
+ *      0 .. nx+2 (the pair load at the clamped column nx+1). A caller's allocation must therefore make elements
+ *          ptr[-ldz]  ..  ptr[(nz+2)*ldz + (ny+1)*ldy + nx + 2]     (at most ptr[(nz+3)*ldz])
+ *      of every field readable: planes -1 .. nz+2 at full pitch and one element more. gs_field_layout's recipe
+ *      provides it (ldz before the origin, the +32 after). This extent is derived from the address arithmetic of
+ *      csrc/gs_device.hpp; the tests show that such reads do not reach a result, not where they stop.
  *  - Stencil: 7 (value, offset) pairs in config order, offsets in {-1,0,1}. The canonical order
  *    (centre, +x, -x, +y, -y, +z, -z) of every reference config runs the LDS/register-tiled fast
  *    kernels; any other order or shape runs a generic kernel. Sums are evaluated in config order.
@@ -269,8 +291,9 @@ int gs_newton_F_update_restrict_bfac(const gs_stencil* S, const gs_level* L, dou
                                      double* coarse_w, const gs_level* coarse, double* b_out, hipStream_t stream);
 
 /* The linearisation factor of GS_NEWTON_B (added): b = gamma*(1+w)*exp(w), in that evaluation order, at every
- * element of planes -1 .. nz+2 of a field laid out by gs_field_layout (interior, boundary and ghost planes, the
- * row padding included), so a Z-slab's B is current wherever its w is. w and b must not overlap. */
+ * element of planes -1 .. nz+2 of a field in any accepted layout — all ldz*(nz+4) words from ptr - ldz on: interior,
+ * boundary and ghost planes, the row padding and plane gaps included — so a Z-slab's B is current wherever its w is.
+ * Both fields must hold those planes (gs_field_layout's do). w and b must not overlap. */
 int gs_newton_bfac(const gs_level* L, double gamma, const double* w, double* b, hipStream_t stream);
 
 /* dst[i] = value for i < n (Vector3::fill, src/cpu/Vector3.cpp:29-32). */
