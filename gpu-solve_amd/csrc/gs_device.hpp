@@ -117,8 +117,6 @@ bool valid_stencil(const gs_stencil* S)
 // initialised at load time: no getenv is reachable from a launch). Defaults are the measured choices
 // (DESIGN.md §9); the switches serve tools/ A/B runs and the tests that pin every alternative path:
 //   GS_NO_UNIT_STENCIL   the general 14-operation stencil sum instead of the unit-neighbour form
-//   GS_TBX_PFD=1         column-block pairs at one plane step of prefetch (default 2)
-//   GS_PAIR_XH=0         rows > 512 points on k_tb2's one-y-wave shape instead of column blocks
 //   GS_FIT_ROUNDS=0      no round-fitted chunk lengths for the zero-iterate pairs
 //   GS_SLAB_ZC=n         z-chunk (planes; even, >= 2) of pair launches past a slab's first plane
 //   GS_PAIR_ZC=n         z-chunk of pair launches from a level's first plane (>= 2^26 points)
@@ -127,25 +125,20 @@ bool valid_stencil(const gs_stencil* S)
 //   GS_PAIR_ONE_ROUND=0  no one-round / four-round chunking on >= 2^26-point levels
 //   GS_RR_LDS            residual + restriction through the LDS kernel (k_resrestrict) only
 //   GS_RR_NR=1|2         coarse rows per k_rr2 block (default: 2 on LINEAR levels of >= 2^26 points)
-//   GS_RR_NTU=0|1        k_rr2 non-temporal loads never / on two-row blocks only (default 2: every block, r05w)
 //   GS_RR_REVERSE=0|1    k_rr2 z-chunks in ascending (0) or descending (1, default: r04e, -1% on 512^3) order
 //   GS_NO_ZERO_Q         zero-iterate sweeps evaluate the stencil of their zeros instead of taking q = +0
 //   GS_XH_SWIZZLE=0|1    column-block pairs: the mirrored row's x-waves rotated by two (1, default) or not (0)
 //   GS_MID_ZC=n          z-chunk of pair launches over whole levels of < 2^26 points (A/B)
 //   GS_RR_ZC=n           z-chunk (coarse planes) of k_rr2 launches from fine levels of < 2^26 points (A/B)
 //   GS_RR_ZC_BIG=n       the same for fine levels of >= 2^26 points (A/B)
-//   GS_PAIR_ONE_ROUND_MID=1 LINEAR pair launches over levels of 2^24 .. 2^26 points in one round of blocks (A/B)
 //   GS_RB_ZC=n           z-chunk of the one-point passes (k_rb sweeps / residuals, the Newton update pass) (A/B)
-//   GS_NEWTON_XH=0       NEWTON plain pairs on rows of 513-1024 points through k_tb2 instead of column blocks (A/B)
-//   GS_SPEC_CACHED=1     pairs with norm partials store through the caches, not non-temporally (A/B)
-//   GS_RR_NG=2           k_rr2 with two groups of coarse rows per block (default 1: measured faster, r05b)
 //   GS_PAIR_FX=0         LINEAR plain pairs always through the instance with per-lane range selects (A/B, r06)
 //   GS_FMG_NT=0|1        gs_fmg_prolong's fine stores never / always non-temporal (default: from 2^25 fine points) (A/B)
 //   GS_T3_SADDR=0        the fused triple's unit-stencil instances with per-lane 64-bit addresses (A/B)
 struct Knobs {
-    bool unitStencil, tbxPfd2, pairXh, fitRounds, bigChunks, oneRound, rrLds, zeroQ, newtonXh, specCached;
-    int xhSwizzle, midZc, rrZc, rrZcBig, oneRoundMid, rbZc;
-    int slabZc, pairZc, rrNr, rrNtu, rrReverse, rrNg, rrDma;
+    bool unitStencil, fitRounds, bigChunks, oneRound, rrLds, zeroQ;
+    int xhSwizzle, midZc, rrZc, rrZcBig, rbZc;
+    int slabZc, pairZc, rrNr, rrReverse;
     bool pairFx, t3Saddr;
     int fmgNt;
     int64_t pairMinBlocks;
@@ -155,13 +148,12 @@ struct Knobs {
         return e && *e ? atoi(e) : dflt;
     }
     Knobs()
-        : unitStencil(getenv("GS_NO_UNIT_STENCIL") == nullptr), tbxPfd2(num("GS_TBX_PFD", 2) != 1),
-          pairXh(num("GS_PAIR_XH", 1) != 0), fitRounds(num("GS_FIT_ROUNDS", 1) != 0),
+        : unitStencil(getenv("GS_NO_UNIT_STENCIL") == nullptr), fitRounds(num("GS_FIT_ROUNDS", 1) != 0),
           bigChunks(num("GS_PAIR_BIG_CHUNKS", 1) != 0), oneRound(num("GS_PAIR_ONE_ROUND", 1) != 0),
           rrLds(getenv("GS_RR_LDS") != nullptr), zeroQ(getenv("GS_NO_ZERO_Q") == nullptr),
-          newtonXh(num("GS_NEWTON_XH", 1) != 0), specCached(num("GS_SPEC_CACHED", 0) != 0),
-          xhSwizzle(num("GS_XH_SWIZZLE", 1)), midZc(num("GS_MID_ZC", 0)), rrZc(num("GS_RR_ZC", 0)), rrZcBig(num("GS_RR_ZC_BIG", 0)), oneRoundMid(num("GS_PAIR_ONE_ROUND_MID", 0)), rbZc(num("GS_RB_ZC", 0)), slabZc(num("GS_SLAB_ZC", 0)), pairZc(num("GS_PAIR_ZC", 0)),
-          rrNr(num("GS_RR_NR", 0)), rrNtu(num("GS_RR_NTU", 2)), rrReverse(num("GS_RR_REVERSE", 1)), rrNg(num("GS_RR_NG", 0)), rrDma(num("GS_RR_DMA", 0)),
+          xhSwizzle(num("GS_XH_SWIZZLE", 1)), midZc(num("GS_MID_ZC", 0)), rrZc(num("GS_RR_ZC", 0)),
+          rrZcBig(num("GS_RR_ZC_BIG", 0)), rbZc(num("GS_RB_ZC", 0)), slabZc(num("GS_SLAB_ZC", 0)),
+          pairZc(num("GS_PAIR_ZC", 0)), rrNr(num("GS_RR_NR", 0)), rrReverse(num("GS_RR_REVERSE", 1)),
           pairFx(num("GS_PAIR_FX", 1) != 0), t3Saddr(num("GS_T3_SADDR", 1) != 0), fmgNt(num("GS_FMG_NT", -1)),
           pairMinBlocks(num("GS_PAIR_MIN_BLOCKS", 128))
     {
@@ -1241,20 +1233,16 @@ __global__ __launch_bounds__(RR_T) void k_resrestrict(Coef k, StencilOffsets so,
 // column (2X+1) is one more DPP shift (the right wave's lane 0 through LDS). The 27 terms are summed in
 // the reference's order (CpuSolver.cpp:225-231): 16 B of compulsory HBM reads per fine point (v, f)
 // plus 1 B of coarse writes, the residual never stored, and no LDS staging of the operands (the
-// LDS-tiled k_resrestrict, kept for the other cases, is latency-bound at 2 blocks per CU). PF = true
-// keeps the next coarse plane's loads in flight (two-slot ring, as in k_rb); production runs PF =
-// false: one slot loaded per step, 154 VGPRs and 3 waves per SIMD, measured faster. Blocks go in
+// LDS-tiled k_resrestrict, kept for the other cases, is latency-bound at 2 blocks per CU). A step's
+// operands are loaded at the top of the step into one slot (154 VGPRs and 3 waves per SIMD: measured
+// faster than a two-slot ring that keeps the next plane's loads in flight). Blocks go in
 // XCD-aware order, y fastest, so the neighbouring rows that share 3 of a block's 5 v rows run on the
 // same XCD at the same time.
 constexpr int RR2_WXMAX = 8, RR2_NR2_LOG2_POINTS = 26;
 
 // NR: coarse rows per block (1: fine rows 2Y-1..2Y+1 computed; 2: 2Y-1..2Y+3, the shared row 2Y+1 and three
 // of the seven v rows once instead of twice)
-// NG: groups of WX waves per block, group g owning coarse rows Y + NR g: the groups are y-neighbours that march
-// the same planes in lock-step (the per-plane barrier is the block's), so the v / f rows they share are
-// fetched by the one CU at the same time — an L1 / L2 hit for the second group — instead of by two blocks
-// that drift apart on different CUs (where the shared rows miss the 4 MB L2 a third of the time)
-template <int MODE, bool PF, int NR = 1, bool UN = false, bool NTU = false, int NG = 1> // PF: the next plane's operands in flight (two-slot ring), else loaded per step
+template <int MODE, int NR, bool UN>
 __global__ __launch_bounds__(WAVE* RR2_WXMAX) void k_rr2(Coef k, const double* __restrict__ v,
                                                          const double* __restrict__ f, const double* __restrict__ w,
                                                          double* __restrict__ ca,
@@ -1262,24 +1250,20 @@ __global__ __launch_bounds__(WAVE* RR2_WXMAX) void k_rr2(Coef k, const double* _
                                                          int64_t fldy, int64_t fldz, int cnx, int cny, int cnz, int64_t cldy,
                                                          int64_t cldz, int ZC, int zhi, int rev)
 {
-    static_assert(!newtonish(MODE) || !PF, "NEWTON: newtonV rows exceed the budget of the prefetch ring");
     constexpr int RR = 2 * NR + 1; // computed fine rows; v rows 0 .. RR+1 (0 and RR+1: halo rows)
     // wave-edge columns [parity][1 + wave][side][plane * 3 + row] of v, and r at each wave's first fine
     // column [parity][1 + wave][plane * 3 + row]; slots 0 and WX+1 are the zero x-boundary
-    __shared__ double veA[NG][2][RR2_WXMAX + 2][2][2 * RR];
-    __shared__ double reA[NG][2][RR2_WXMAX + 2][2 * RR];
+    __shared__ double ve[2][RR2_WXMAX + 2][2][2 * RR];
+    __shared__ double re[2][RR2_WXMAX + 2][2 * RR];
     const int lane = threadIdx.x;
     const int wx = __builtin_amdgcn_readfirstlane(threadIdx.y);
-    const int grp = NG > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.z) : 0;
     const int WX = blockDim.y;
-    const int tid = lane + WAVE * (wx + WX * grp);
-    for (int i = tid; i < NG * 2 * (RR2_WXMAX + 2) * 2 * 2 * RR; i += WAVE * WX * NG) (&veA[0][0][0][0][0])[i] = 0.0;
-    for (int i = tid; i < NG * 2 * (RR2_WXMAX + 2) * 2 * RR; i += WAVE * WX * NG) (&reA[0][0][0][0])[i] = 0.0;
+    const int tid = lane + WAVE * wx;
+    for (int i = tid; i < 2 * (RR2_WXMAX + 2) * 2 * 2 * RR; i += WAVE * WX) (&ve[0][0][0][0])[i] = 0.0;
+    for (int i = tid; i < 2 * (RR2_WXMAX + 2) * 2 * RR; i += WAVE * WX) (&re[0][0][0])[i] = 0.0;
     __syncthreads();
-    double (&ve)[2][RR2_WXMAX + 2][2][2 * RR] = veA[grp]; // this group's wave-edge exchange
-    double (&re)[2][RR2_WXMAX + 2][2 * RR] = reA[grp];
     const int64_t tile = xcd_tile(blockIdx.x + (int64_t)gridDim.x * blockIdx.y, (int64_t)gridDim.x * gridDim.y);
-    const int Y = 1 + NR * (NG * (int)(tile % gridDim.x) + grp);
+    const int Y = 1 + NR * (int)(tile % gridDim.x);
     // rev (GS_RR_REVERSE): the z-chunks in descending order, so the first blocks read the planes the
     // preceding pair launch touched last
     const int zi = (int)(tile / gridDim.x);
@@ -1302,36 +1286,36 @@ __global__ __launch_bounds__(WAVE* RR2_WXMAX) void k_rr2(Coef k, const double* _
     };
     // one step's operands: v planes 2Z+1 (A), 2Z+2 (B) of rows 1..3; halo rows 0 / 4 of planes 2Z (H0)
     // and 2Z+1 (H1); f of planes 2Z (F0), 2Z+1 (F1) rows 1..3
-    double2 VA[2][RR], VB[2][RR], H0[2][2], H1[2][2], F0[2][RR], F1[2][RR], W0[2][RR], W1[2][RR];
-    auto load_slot = [&](const int s, const int Z) {
+    double2 VA[RR], VB[RR], H0[2], H1[2], F0[RR], F1[RR], W0[RR], W1[RR];
+    auto load_slot = [&](const int Z) {
         const int p = 2 * Z;
         // the step's halo rows first (the rows the y-neighbour blocks read too), then row by row: k_rr2 0.442-0.443 vs
         // 0.458-0.459 ms LINEAR, 0.7085-0.7088 vs 0.7254-0.7259 ms NEWTON_B per 512^3 launch (r06x / r06y,
         // interleaved, profiles/r06/r06x_load_order_ab.txt; f rows first: 0.449 / 0.726-0.740, plane by plane: 0.484-0.485 /
         // 0.754-0.760, v / f / w grouped: 0.481-0.485 / 0.747-0.750, halos then v then f / w: 0.476-0.478 / 0.751)
-        H0[s][0] = ld2(at(v, 0, p));
-        H0[s][1] = ld2(at(v, RR + 1, p));
-        H1[s][0] = ld2(at(v, 0, p + 1));
-        H1[s][1] = ld2(at(v, RR + 1, p + 1));
+        H0[0] = ld2(at(v, 0, p));
+        H0[1] = ld2(at(v, RR + 1, p));
+        H1[0] = ld2(at(v, 0, p + 1));
+        H1[1] = ld2(at(v, RR + 1, p + 1));
 #pragma unroll
         for (int j = 0; j < RR; j++) {
-            // NTU: rows no neighbouring block reads (v: 2Y+1 .. 2Y+2NR-3, f: 2Y .. 2Y+2NR-2) bypass L2
-            // retention, leaving it to the shared halo rows
-            const bool uv = NTU && j >= 2 && j <= RR - 3, uf = NTU && j >= 1 && j <= RR - 2;
-            VA[s][j] = uv ? ld2s<true>(at(v, j + 1, p + 1)) : ld2(at(v, j + 1, p + 1));
-            VB[s][j] = uv ? ld2s<true>(at(v, j + 1, p + 2)) : ld2(at(v, j + 1, p + 2));
-            F0[s][j] = uf ? ld2s<true>(at(f, j + 1, p)) : ld2(at(f, j + 1, p));
-            F1[s][j] = uf ? ld2s<true>(at(f, j + 1, p + 1)) : ld2(at(f, j + 1, p + 1));
+            // rows no neighbouring block reads (v: 2Y+1 .. 2Y+2NR-3, f: 2Y .. 2Y+2NR-2) are non-temporal loads:
+            // they bypass L2 retention, leaving it to the shared halo rows
+            const bool uv = j >= 2 && j <= RR - 3, uf = j >= 1 && j <= RR - 2;
+            VA[j] = uv ? ld2s<true>(at(v, j + 1, p + 1)) : ld2(at(v, j + 1, p + 1));
+            VB[j] = uv ? ld2s<true>(at(v, j + 1, p + 2)) : ld2(at(v, j + 1, p + 2));
+            F0[j] = uf ? ld2s<true>(at(f, j + 1, p)) : ld2(at(f, j + 1, p));
+            F1[j] = uf ? ld2s<true>(at(f, j + 1, p + 1)) : ld2(at(f, j + 1, p + 1));
             if (MODE == GS_NEWTON_B && k.bconst) {
-                W0[s][j] = make_double2(k.gamma, k.gamma);
-                W1[s][j] = W0[s][j];
+                W0[j] = make_double2(k.gamma, k.gamma);
+                W1[j] = W0[j];
             } else if (newtonish(MODE)) {
-                W0[s][j] = uf ? ld2s<true>(at(w, j + 1, p)) : ld2(at(w, j + 1, p));
-                W1[s][j] = uf ? ld2s<true>(at(w, j + 1, p + 1)) : ld2(at(w, j + 1, p + 1));
+                W0[j] = uf ? ld2s<true>(at(w, j + 1, p)) : ld2(at(w, j + 1, p));
+                W1[j] = uf ? ld2s<true>(at(w, j + 1, p + 1)) : ld2(at(w, j + 1, p + 1));
             }
         }
     };
-    // LDS-only barrier: the outstanding prefetch stays in flight across it
+    // LDS-only barrier
     auto lds_barrier = [] { GS_LDS_BARRIER(); }; // lgkmcnt(0), s_barrier
     // the columns left of lane 0 / right of lane 63 on two planes: v(x-1) of lane 0, v(x+2) of lane 63
     auto edges_v = [&](int par, const double2 (&P)[RR], const double2 (&Q)[RR], double (&CLp)[RR], double (&CRp)[RR],
@@ -1420,21 +1404,18 @@ __global__ __launch_bounds__(WAVE* RR2_WXMAX) void k_rr2(Coef k, const double* _
 #pragma unroll
         for (int j = 0; j < RR; j++) Vm[j] = Vq[j]; // window: Vm = v(2Zb-1), V0 = v(2Zb)
     }
-    if (PF) load_slot(1, Zb);
     // Both halves always run (an odd chunk ends with a step whose results are discarded), and every
-    // load is unconditional (plane indices clamped), so the slots keep fixed registers.
+    // load is unconditional (plane indices clamped), so the slot keeps fixed registers.
     for (int z0 = Zb; z0 <= Ze; z0 += 2) {
 #pragma unroll
         for (int ph = 0; ph < 2; ph++) {
             const int Z = z0 + ph;
-            const int cs = PF ? ph ^ 1 : 0; // slot holding this step's operands
-            if (PF) load_slot(ph, Z + 1);
-            else load_slot(0, Z);
+            load_slot(Z);
             double CL0[RR], CR0[RR], CL1[RR], CR1[RR];
-            edges_v(ph, V0, VA[cs], CL0, CR0, CL1, CR1);
+            edges_v(ph, V0, VA, CL0, CR0, CL1, CR1);
             double2 R0[RR], R1[RR];
-            resid(Vm, V0, H0[cs], VA[cs], F0[cs], W0[cs], CL0, CR0, 2 * Z, R0);
-            resid(V0, VA[cs], H1[cs], VB[cs], F1[cs], W1[cs], CL1, CR1, 2 * Z + 1, R1);
+            resid(Vm, V0, H0, VA, F0, W0, CL0, CR0, 2 * Z, R0);
+            resid(V0, VA, H1, VB, F1, W1, CL1, CR1, 2 * Z + 1, R1);
             double N0[RR], N1[RR];
             edges_r(ph, R0, R1, N0, N1);
 #pragma unroll
@@ -1462,273 +1443,13 @@ __global__ __launch_bounds__(WAVE* RR2_WXMAX) void k_rr2(Coef k, const double* _
             }
 #pragma unroll
             for (int j = 0; j < RR; j++) {
-                Vm[j] = VA[cs][j];
-                V0[j] = VB[cs][j];
+                Vm[j] = VA[j];
+                V0[j] = VB[j];
                 Rm[j] = R1[j];
                 Nm[j] = N1[j];
             }
         }
     }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Residual + full weighting with an LDS-DMA operand ring ("rr2d", r06; verdict r05 item 1). Same arithmetic,
-// term order and outputs as k_rr2 (bit-identical), built for the case k_rr2 handles worst: its operands of a plane
-// step are loaded at the top of the step and waited for at once (no register room for a prefetch ring: PF = false),
-// so at two waves per SIMD the loads are exposed every step (PMC wait_inst 0.43-0.46 of wave cycles).
-// Here the operands never occupy VGPRs while in flight: every wave streams ITS OWN columns of the operand rows of
-// fine plane p + 2 straight into an LDS ring (global_load_lds_dwordx4, one instruction per row and wave, inline asm:
-// M0 is written in the statement that reads it) while it computes plane p, and waits for plane p's with a hand-
-// counted s_waitcnt vmcnt before the step's one barrier. A ring slot holds what the residual of fine plane p adds to
-// the register window (v of planes p-1, p): v of plane p+1 on the computed rows, the two halo rows of plane p, f
-// (and NEWTON's w) of plane p, RR + 2 + RR (+ RR) rows of the block's width; three slots (plane p read, p+1 and p+2
-// in flight). The wave-edge columns x-1 / x+2 of every v row are read straight from the neighbouring waves' columns
-// of the slot (LDS broadcast reads, one plane early), so only r's wave-edge column still goes through an exchange.
-// One fine plane per step; the restriction of coarse plane Z runs at step 2Z+2, once r of plane 2Z+1 has crossed
-// the wave edges with that step's barrier.
-// The counted wait is exact because every VMEM operation of the loop is accounted for: RROWS DMA instructions per
-// step and 2 NR coarse stores at every even step, stores that never branch away (an invalid point writes to a sink
-// word instead); so before the wait of step p exactly one plane's DMA group and one store group are younger than
-// plane p's DMA group (the prologue issues one group of sink stores to make step p0 look the same).
-// LDS: 3 slots x RROWS rows x WX KB (512-point rows: 144 KB LINEAR NR = 2, 132 KB NEWTON NR = 1): one block per CU.
-constexpr int RR2D_WXMAX = 4, RR2D_SLOTS = 3;
-__device__ double gs_rr2d_sink[2 * WAVE]; // where the unconditional stores of invalid points go
-
-template <int MODE, int NR, bool WR>
-constexpr int rr2d_rows()
-{
-    return (2 * NR + 1) * (WR ? 3 : 2) + 2;
-}
-
-template <int N>
-__device__ __forceinline__ void rr2d_wait()
-{
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"i"(N) : "memory");
-}
-
-// 16 B per lane from gsrc into LDS at byte address lds_dst + 16 lane (lds_dst wave-uniform)
-__device__ __forceinline__ void rr2d_dma(const double* gsrc, unsigned lds_dst)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds_dst)
-                 : "memory");
-}
-
-template <int MODE, int NR, bool UN, bool WR>
-__global__ __launch_bounds__(WAVE* RR2D_WXMAX) void k_rr2d(Coef k, const double* __restrict__ v,
-                                                           const double* __restrict__ f, const double* __restrict__ w,
-                                                           double* __restrict__ ca, double* __restrict__ cb, int fnx,
-                                                           int fny, int fnz, int64_t fldy, int64_t fldz, int cnx,
-                                                           int cny, int cnz, int64_t cldy, int64_t cldz, int ZC, int zhi)
-{
-    constexpr int RR = 2 * NR + 1;                   // computed fine rows; v rows 0 .. RR+1 (0, RR+1: halo rows)
-    constexpr int RROWS = rr2d_rows<MODE, NR, WR>(); // ring rows per slot (= DMA instructions per wave and step)
-    constexpr int RV = 0, RH = RR, RF = RR + 2, RW = 2 * RR + 2; // first row of each operand in a slot
-    constexpr int NSTORE = 2 * NR;                               // coarse stores per wave at an even step
-    constexpr int NWAIT = RROWS + NSTORE;                        // VMEM operations younger than the awaited plane's
-    static_assert(NWAIT <= 63, "vmcnt field");
-    extern __shared__ double ring[]; // [slot][row][WX * 128 doubles]; then re, ve
-    const int lane = threadIdx.x;
-    const int wx = __builtin_amdgcn_readfirstlane(threadIdx.y);
-    const int WX = blockDim.y;
-    const int RS = WX * 2 * WAVE; // doubles per ring row
-    double* re = ring + RR2D_SLOTS * RROWS * RS; // r(2X+1) edges: [parity][1 + wave][row]
-    double* ve = re + 2 * (RR2D_WXMAX + 2) * RR;  // prologue v edges: [1 + wave][side][row]
-    const int tid = lane + WAVE * wx;
-    for (int i = tid; i < 2 * (RR2D_WXMAX + 2) * RR + (RR2D_WXMAX + 2) * 2 * RR; i += WAVE * WX) re[i] = 0.0;
-    const int64_t tile = xcd_tile(blockIdx.x + (int64_t)gridDim.x * blockIdx.y, (int64_t)gridDim.x * gridDim.y);
-    const int Y = 1 + NR * (int)(tile % gridDim.x);
-    const int Zb = 1 + (int)(tile / gridDim.x) * ZC, Ze = min(Zb + ZC - 1, cnz);
-    const int X = 1 + wx * WAVE + lane;
-    const int x = 2 * X - 1, xl = min(x, fnx + 1);
-    const bool okx0 = x <= fnx, okx1 = x + 1 <= fnx;
-    int64_t roff[RR + 2];
-    bool rowc[RR + 2];
-#pragma unroll
-    for (int j = 0; j < RR + 2; j++) {
-        const int y = 2 * Y - 2 + j;
-        roff[j] = (int64_t)min(max(y, 0), fny + 1) * fldy;
-        rowc[j] = y >= 1 && y <= fny;
-    }
-    auto at = [&](const double* b, int j, int p) {
-        return b + xl + roff[j] + (int64_t)min(max(p, 0), fnz + 1 + zhi) * fldz;
-    };
-    typedef __attribute__((address_space(3))) double* lds_dp;
-    const unsigned lbase = (unsigned)(uintptr_t)(lds_dp)ring;
-    // this wave's 1 KB of ring row r of slot s, as an LDS byte address (wave-uniform)
-    auto dst = [&](int s, int r) {
-        return (unsigned)__builtin_amdgcn_readfirstlane((int)(lbase + 8u * (unsigned)((s * RROWS + r) * RS + wx * 2 * WAVE)));
-    };
-    // the operand rows of fine plane p into slot s
-    auto dma_plane = [&](int s, int p) {
-#pragma unroll
-        for (int j = 0; j < RR; j++) rr2d_dma(at(v, j + 1, p + 1), dst(s, RV + j));
-        rr2d_dma(at(v, 0, p), dst(s, RH));
-        rr2d_dma(at(v, RR + 1, p), dst(s, RH + 1));
-#pragma unroll
-        for (int j = 0; j < RR; j++) rr2d_dma(at(f, j + 1, p), dst(s, RF + j));
-        if constexpr (WR) {
-#pragma unroll
-            for (int j = 0; j < RR; j++) rr2d_dma(at(w, j + 1, p), dst(s, RW + j));
-        }
-    };
-    auto row_at = [&](int s, int r) { return ring + (s * RROWS + r) * RS; };
-    auto lds2 = [&](int s, int r) { return *reinterpret_cast<const double2*>(row_at(s, r) + wx * 2 * WAVE + 2 * lane); };
-    double* sink = gs_rr2d_sink;
-
-    // r = f - A v on fine plane p (k_rr2's resid: same expression, same term order; 0 outside the interior), with the
-    // plane's 2 RR divisions by h^2 batched behind one range branch (div_hh_n: the same quotients bit for bit) — at
-    // one wave per SIMD a branch per point would expose every point's latency
-    auto resid = [&](const double2 (&Vm)[RR], const double2 (&Vc)[RR], const double2 (&H)[2], const double2 (&Vp)[RR],
-                     const double2 (&F)[RR], const double2 (&W)[RR], const double (&CL)[RR], const double (&CR)[RR], int p,
-                     double2 (&R)[RR]) {
-        const bool pin = p >= 1 && (p <= fnz || (zhi && p == fnz + 1));
-        double q[2 * RR];
-#pragma unroll
-        for (int j = 0; j < RR; j++) {
-            const double2 c = Vc[j];
-            const double2 ym = j == 0 ? H[0] : Vc[j - 1], yp = j == RR - 1 ? H[1] : Vc[j + 1];
-            const double xm0 = lane_from_left<true>(c.y, CL[j]);
-            const double xp1 = lane_from_right<true>(c.x, CR[j]);
-            q[2 * j] = stencil_sum<UN>(k, c.x, c.y, xm0, yp.x, ym.x, Vp[j].x, Vm[j].x);
-            q[2 * j + 1] = stencil_sum<UN>(k, c.y, xp1, c.x, yp.y, ym.y, Vp[j].y, Vm[j].y);
-        }
-        div_hh_n(k, q);
-#pragma unroll
-        for (int j = 0; j < RR; j++) {
-            const double w0 = newtonish(MODE) ? W[j].x : 0.0, w1 = newtonish(MODE) ? W[j].y : 0.0;
-            const double a0 = op_finish<MODE>(k, q[2 * j], Vc[j].x, w0);
-            const double a1 = op_finish<MODE>(k, q[2 * j + 1], Vc[j].y, w1);
-            const bool ok = pin && rowc[j + 1];
-            R[j] = make_double2((ok && okx0) ? F[j].x - a0 : 0.0, (ok && okx1) ? F[j].y - a1 : 0.0);
-        }
-    };
-
-    // prologue: the window v(p0 - 1), v(p0) (p0 = 2Zb - 1) by ordinary loads, v(p0)'s wave-edge columns through LDS
-    const int p0 = 2 * Zb - 1;
-    double2 Vm[RR], V0[RR];
-    double CL0[RR], CR0[RR];
-#pragma unroll
-    for (int j = 0; j < RR; j++) {
-        Vm[j] = ld2(at(v, j + 1, p0 - 1));
-        V0[j] = ld2(at(v, j + 1, p0));
-    }
-    __syncthreads(); // (the zeroed re / ve)
-    if (lane == 0) {
-#pragma unroll
-        for (int j = 0; j < RR; j++) ve[((wx + 1) * 2 + 0) * RR + j] = V0[j].x;
-    }
-    if (lane == WAVE - 1) {
-#pragma unroll
-        for (int j = 0; j < RR; j++) ve[((wx + 1) * 2 + 1) * RR + j] = V0[j].y;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < RR; j++) {
-        CL0[j] = uniform_d(ve[(wx * 2 + 1) * RR + j]);
-        CR0[j] = uniform_d(ve[((wx + 2) * 2 + 0) * RR + j]);
-    }
-    // (every ordinary load above is complete: the ve writes needed them)
-    dma_plane(p0 % RR2D_SLOTS, p0);
-    dma_plane((p0 + 1) % RR2D_SLOTS, p0 + 1);
-#pragma unroll
-    for (int i = 0; i < NSTORE; i++) // the store group step p0's count expects (volatile: never merged or dropped)
-        *reinterpret_cast<volatile double*>(sink + (i & 1) * WAVE + lane) = 0.0;
-
-    double2 Ra[RR], Rb[RR], Rc[RR]; // r of planes p-3, p-2, p-1 entering step p
-    double Na[RR], Nb[RR];          // r(2X+1) of planes p-3, p-2
-#pragma unroll
-    for (int j = 0; j < RR; j++) {
-        Ra[j] = Rb[j] = Rc[j] = make_double2(0.0, 0.0);
-        Na[j] = Nb[j] = 0.0;
-    }
-    const int pe = 2 * Ze + 2;
-    auto step = [&](const int p, const bool even) {
-        const int s = p % RR2D_SLOTS;
-        rr2d_wait<NWAIT>();                              // plane p landed (every wave), slot p-1 read by every wave
-        dma_plane((p + 2) % RR2D_SLOTS, p + 2);          // into the slot plane p-1 used
-        double2 Vn[RR], H[2], F[RR], W[RR];
-        double CLn[RR], CRn[RR], En[RR];
-        // every LDS read of the step first, none under a branch (one wait for all of them): v(p+1)'s wave-edge
-        // columns for the next step (from clamped columns, zero beyond the level's x-boundaries), r(2X+1) of plane
-        // p-1 (its edge word written last step, visible past this step's barrier)
-        const int cl = wx > 0 ? wx * 2 * WAVE - 1 : 0, cr = wx + 1 < WX ? (wx + 1) * 2 * WAVE : 0;
-        const double* rprev = re + ((p - 1) & 1) * (RR2D_WXMAX + 2) * RR + (wx + 2) * RR;
-#pragma unroll
-        for (int j = 0; j < RR; j++) {
-            Vn[j] = lds2(s, RV + j);
-            F[j] = lds2(s, RF + j);
-            if constexpr (WR) W[j] = lds2(s, RW + j);
-            else if constexpr (MODE == GS_NEWTON_B) W[j] = make_double2(k.gamma, k.gamma); // (GS_NEWTON_G)
-            else W[j] = make_double2(0.0, 0.0);
-            CLn[j] = row_at(s, RV + j)[cl];
-            CRn[j] = row_at(s, RV + j)[cr];
-            En[j] = rprev[j];
-        }
-        H[0] = lds2(s, RH);
-        H[1] = lds2(s, RH + 1);
-#pragma unroll
-        for (int j = 0; j < RR; j++) {
-            CLn[j] = wx > 0 ? uniform_d(CLn[j]) : 0.0;
-            CRn[j] = wx + 1 < WX ? uniform_d(CRn[j]) : 0.0;
-        }
-        double2 R[RR];
-        resid(Vm, V0, H, Vn, F, W, CL0, CR0, p, R);
-        double Nc[RR];
-#pragma unroll
-        for (int j = 0; j < RR; j++) Nc[j] = lane_from_right<true>(Rc[j].x, uniform_d(En[j]));
-        // plane p's edge word, for the next step
-        if (lane == 0) {
-#pragma unroll
-            for (int j = 0; j < RR; j++) re[(p & 1) * (RR2D_WXMAX + 2) * RR + (wx + 1) * RR + j] = R[j].x;
-        }
-        if (even) { // restriction of coarse plane Z = p / 2 - 1 from r of planes 2Z-1 .. 2Z+1 = p-3 .. p-1
-            const int Z = p / 2 - 1;
-#pragma unroll
-            for (int i = 0; i < NR; i++) {
-                double acc = 0.0;
-#pragma unroll
-                for (int a = -1; a <= 1; a++)
-#pragma unroll
-                    for (int b = -1; b <= 1; b++)
-#pragma unroll
-                        for (int c = -1; c <= 1; c++) {
-                            const double wgt = 0.125 * ((2.0 - (a < 0 ? -a : a)) / 2.0) *
-                                               ((2.0 - (b < 0 ? -b : b)) / 2.0) * ((2.0 - (c < 0 ? -c : c)) / 2.0);
-                            const int j = 2 * i + b + 1;
-                            const double2 rp = c < 0 ? Ra[j] : (c == 0 ? Rb[j] : Rc[j]);
-                            const double rn = c < 0 ? Na[j] : (c == 0 ? Nb[j] : Nc[j]);
-                            acc += wgt * (a < 0 ? rp.x : (a == 0 ? rp.y : rn));
-                        }
-                const bool ok = Z >= Zb && Z <= Ze && X <= cnx && Y + i <= cny;
-                const int64_t q = X + (Y + i) * cldy + (int64_t)Z * cldz;
-                double* pa = ok ? ca + q : sink + lane;
-                double* pb = (ok && cb) ? cb + q : sink + WAVE + lane;
-                *pa = acc;
-                *pb = acc;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < RR; j++) {
-            Vm[j] = V0[j];
-            V0[j] = Vn[j];
-            CL0[j] = CLn[j];
-            CR0[j] = CRn[j];
-            Ra[j] = Rb[j];
-            Rb[j] = Rc[j];
-            Rc[j] = R[j];
-            Na[j] = Nb[j];
-            Nb[j] = Nc[j];
-        }
-    };
-    for (int p = p0; p <= pe; p += 2) {
-        step(p, false);
-        step(p + 1, true);
-    }
-    // drain: the last DMAs must land before the block's LDS can be reused by another block
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2516,185 +2237,14 @@ bool bad_level(const gs_level* L)
 // planes are current) its value is the boundary value itself, exactly as a stored sweep would leave
 // it. Per point the arithmetic is the single sweep's, so the result is bit-identical to two
 // gs_jacobi_sweep calls.
-template <int MODE, int RY, int WXMAX, bool NT, bool NTF = NT, bool ZV = false>
-__global__ __launch_bounds__(WAVE* WXMAX) void k_tb2(Coef k, const double* __restrict__ v,
-                                                      const double* __restrict__ f, const double* __restrict__ w,
-                                                      double* __restrict__ out, double* __restrict__ partials, int nx,
-                                                      int ny, int nz, int64_t ldy, int64_t ldz, int ZC, int zlo,
-                                                      int zhi, const double*, const double*, int, int, int, int64_t,
-                                                      int64_t, const double*)
-{
-    __shared__ double red[WXMAX];
-    double sumsq = 0.0; // r^2 of sweep 1's residual over the block's own points (partials != NULL)
-    constexpr int NV = RY + 2;  // sweep-1 rows (j = 1..RY+2 <-> y0-1..y0+RY)
-    constexpr int NE = NV + RY; // LDS edge values per wave side: v rows + sweep-1 rows
-    // edge[parity][1 + wave][side][value]; slots 0 and WX+1 are virtual waves holding the x-boundary
-    // columns, which this kernel takes to be zero (the reference's homogeneous Dirichlet boundary:
-    // v's boundary cells are never written)
-    __shared__ double edge[2][WXMAX + 2][2][NE];
-    const int lane = threadIdx.x;
-    const int wx = __builtin_amdgcn_readfirstlane(threadIdx.y);
-    const int WX = blockDim.y;
-    for (int i = threadIdx.x + threadIdx.y * WAVE; i < 2 * (WXMAX + 2) * 2 * NE; i += WAVE * WX)
-        (&edge[0][0][0][0])[i] = 0.0;
-    __syncthreads();
-    const int x0 = 1 + wx * (2 * WAVE);
-    const int x = x0 + 2 * lane;
-    const int xl = min(x, nx + 1);
-    const bool bx0 = x > nx, bx1 = x + 1 > nx;            // boundary / beyond columns
-    const bool okx0 = x <= nx, okx1 = x + 1 <= nx;
-    // XCD-aware order (cdna_hip_programming.md T1): hardware block b runs on XCD b % 8, so logical
-    // tiles are dealt out in contiguous runs per XCD, y-tile fastest: the blocks an XCD runs at one
-    // time are y-neighbours marching the same planes, and the halo rows one of them re-reads were
-    // just fetched into that XCD's L2 by its neighbour.
-    const int64_t tile = xcd_tile(blockIdx.x + (int64_t)gridDim.x * blockIdx.y, (int64_t)gridDim.x * gridDim.y);
-    const int y0 = 1 + (int)(tile % gridDim.x) * RY;
-    const int zb = 1 + (int)(tile / gridDim.x) * ZC;
-    const int ze = min(zb + ZC - 1, nz);
-
-    int64_t roff[RY + 4]; // rows y0-2 .. y0+RY+1
-    bool rowc[RY + 4];    // row is a computable interior row
-#pragma unroll
-    for (int j = 0; j < RY + 4; j++) {
-        const int y = y0 - 2 + j;
-        roff[j] = (int64_t)min(max(y, 0), ny + 1) * ldy;
-        rowc[j] = y >= 1 && y <= ny;
-    }
-    auto planeok = [&](int z) { return (z >= 1 && z <= nz) || (z == 0 && zlo) || (z == nz + 1 && zhi); };
-    auto at = [&](const double* base, int j, int z) { return base + xl + roff[j] + (int64_t)z * ldz; };
-
-    // Register window (rows j = 1..NV of the v planes; rows 0 and RY+3 only as halo pairs): Vp, Vc =
-    // v at planes z-1, z; V1p, V1c = sweep-1 values at planes z-2, z-1; Fprev, Wprev = f, w at z-1.
-    // What step z loads (v rows of plane z+2, f / w rows and the halo rows of plane z+1) goes into
-    // slot ph of a two-slot ring and is consumed from there one step later before being moved on,
-    // so every wait lands a full step of arithmetic after its load (loop unrolled by two).
-    double2 Vp[NV], Vc[NV], VL[2][NV], FL[2][NV], WL[2][NV], HL[2][2];
-    double2 V1p[RY], V1c[NV], Fprev[RY], Wprev[RY];
-#pragma unroll
-    for (int j = 0; j < NV; j++) V1c[j] = make_double2(0.0, 0.0);
-#pragma unroll
-    for (int j = 0; j < RY; j++) V1p[j] = make_double2(0.0, 0.0);
-    // slot s <- plane z's f, w, halo rows and plane zv's v rows
-    auto load_slot = [&](const int s, const int z, const int zv) {
-#pragma unroll
-        for (int j = 1; j <= NV; j++) {
-            VL[s][j - 1] = ldv2<ZV>(at(v, j, zv));
-            FL[s][j - 1] = ld2s<NTF>(at(f, j, z));
-            if (newtonish(MODE)) WL[s][j - 1] = ld2(at(w, j, z));
-        }
-        HL[s][0] = ldv2<ZV>(at(v, 0, z));
-        HL[s][1] = ldv2<ZV>(at(v, RY + 3, z));
-    };
-#pragma unroll
-    for (int j = 1; j <= NV; j++) {
-        Vp[j - 1] = ldv2<ZV>(at(v, j, zb - 2));
-        Vc[j - 1] = ldv2<ZV>(at(v, j, zb - 1));
-    }
-    load_slot(1, zb - 1, zb);
-    // Both halves always run (an odd step count ends with one step whose results are discarded) and
-    // every load is unconditional (plane indices clamped into the padded range), so the slots keep
-    // fixed registers around the loop.
-    for (int z0 = zb - 1; z0 <= ze + 1; z0 += 2) {
-#pragma unroll
-        for (int ph = 0; ph < 2; ph++) {
-            const int z = z0 + ph;
-            const int cs = ph ^ 1; // slot holding plane z (and v of plane z+1)
-            load_slot(ph, min(z + 1, nz + 1), min(z + 2, nz + 2));
-            // ---- exchange the columns just outside each wave: v(z) rows 1..NV, sweep-1(z-1) rows 2..RY+1 ----
-            if (lane == 0) {
-#pragma unroll
-                for (int j = 1; j <= NV; j++) edge[ph][wx + 1][0][j - 1] = Vc[j - 1].x;
-#pragma unroll
-                for (int j = 2; j <= RY + 1; j++) edge[ph][wx + 1][0][NV + j - 2] = V1c[j - 1].x;
-            }
-            if (lane == WAVE - 1) {
-#pragma unroll
-                for (int j = 1; j <= NV; j++) edge[ph][wx + 1][1][j - 1] = Vc[j - 1].y;
-#pragma unroll
-                for (int j = 2; j <= RY + 1; j++) edge[ph][wx + 1][1][NV + j - 2] = V1c[j - 1].y;
-            }
-            // LDS-only barrier: the outstanding prefetch must stay in flight across it
-            __builtin_amdgcn_s_waitcnt(0xc07f); // lgkmcnt(0)
-            __builtin_amdgcn_s_barrier();
-            double CL[NE], CR[NE];
-#pragma unroll
-            for (int i = 0; i < NE; i++) {
-                CL[i] = edge[ph][wx][1][i];     // wave wx-1 (slot 0: the zero x = 0 boundary)
-                CR[i] = edge[ph][wx + 2][0][i]; // wave wx+1 (slot WX+1: the zero x = nx+1 boundary)
-            }
-
-            // ---- sweep 1 at plane z ----
-            double2 V1n[NV];
-            const bool pz = planeok(z);
-#pragma unroll
-            for (int j = 1; j <= NV; j++) {
-                const double2 c = Vc[j - 1], zm = Vp[j - 1], zp = VL[cs][j - 1];
-                const double2 ym = j == 1 ? HL[cs][0] : Vc[j - 2], yp = j == NV ? HL[cs][1] : Vc[j];
-                const double xm0 = lane_from_left<true>(c.y, CL[j - 1]);
-                const double xp1 = lane_from_right<true>(c.x, CR[j - 1]);
-                const double wx0 = newtonish(MODE) ? WL[cs][j - 1].x : 0.0;
-                const double wx1 = newtonish(MODE) ? WL[cs][j - 1].y : 0.0;
-                const double a0 = op_value<MODE>(k, c.x, c.y, xm0, yp.x, ym.x, zp.x, zm.x, wx0);
-                const double a1 = op_value<MODE>(k, c.y, xp1, c.x, yp.y, ym.y, zp.y, zm.y, wx1);
-                const double r0 = FL[cs][j - 1].x - a0, r1 = FL[cs][j - 1].y - a1;
-                const double n0 = jacobi_update<MODE>(k, c.x, r0, wx0, k.omega[0]);
-                const double n1 = jacobi_update<MODE>(k, c.y, r1, wx1, k.omega[0]);
-                if (partials && j >= 2 && j <= RY + 1 && z >= zb && z <= ze && rowc[j]) {
-                    if (okx0) sumsq += r0 * r0;
-                    if (okx1) sumsq += r1 * r1;
-                }
-                const bool keep = !pz || !rowc[j];
-                V1n[j - 1] = make_double2((keep || bx0) ? c.x : n0, (keep || bx1) ? c.y : n1);
-            }
-            // ---- sweep 2 at plane z-1 ----
-            if (z - 1 >= zb && z - 1 <= ze) {
-                const int64_t zo = (int64_t)(z - 1) * ldz;
-#pragma unroll
-                for (int j = 2; j <= RY + 1; j++) {
-                    const double2 c = V1c[j - 1], ym = V1c[j - 2], yp = V1c[j], zm = V1p[j - 2], zp = V1n[j - 1];
-                    const double xm0 = lane_from_left<true>(c.y, CL[NV + j - 2]);
-                    const double xp1 = lane_from_right<true>(c.x, CR[NV + j - 2]);
-                    const double wx0 = newtonish(MODE) ? Wprev[j - 2].x : 0.0;
-                    const double wx1 = newtonish(MODE) ? Wprev[j - 2].y : 0.0;
-                    const double a0 = op_value<MODE>(k, c.x, c.y, xm0, yp.x, ym.x, zp.x, zm.x, wx0);
-                    const double a1 = op_value<MODE>(k, c.y, xp1, c.x, yp.y, ym.y, zp.y, zm.y, wx1);
-                    const double o0 = jacobi_update<MODE>(k, c.x, Fprev[j - 2].x - a0, wx0, k.omega[1]);
-                    const double o1 = jacobi_update<MODE>(k, c.y, Fprev[j - 2].y - a1, wx1, k.omega[1]);
-                    if (y0 - 2 + j <= ny) {
-                        double* q = out + x + roff[j] + zo;
-                        if (okx1) st2s<NT>(q, o0, o1);
-                        else if (okx0) *q = o0;
-                    }
-                }
-            }
-            // ---- rotate (only registers whose loads were consumed above) ----
-#pragma unroll
-            for (int j = 0; j < RY; j++) {
-                V1p[j] = V1c[j + 1];
-                Fprev[j] = FL[cs][j + 1];
-                if (newtonish(MODE)) Wprev[j] = WL[cs][j + 1];
-            }
-#pragma unroll
-            for (int j = 0; j < NV; j++) {
-                V1c[j] = V1n[j];
-                Vp[j] = Vc[j];
-                Vc[j] = VL[cs][j];
-            }
-        }
-    }
-    if (partials) {
-        const double t = block_sum<WXMAX>(sumsq, red, WX);
-        if (threadIdx.x == 0 && threadIdx.y == 0) partials[tile] = t;
-    }
-}
-
-// The fused pair with two wave-rows per block ("tb2y"): the block is WX waves along x (the whole row)
+//
+// The kernel ("tb2y") has two wave-rows per block: the block is WX waves along x (the whole row)
 // times 2 waves along y; the y-wave 0 owns output rows y0..y0+RY-1, the y-wave 1 rows
 // y0+RY..y0+2RY-1. Between the two, the rows they need of each other (v of plane z and sweep-1 of
 // plane z-1 at the shared edge) pass through LDS instead of being re-read and recomputed, so a block
 // of 2RY output rows recomputes only ONE sweep-1 halo row per side and reads v rows y0-2..y0+2RY+1,
 // f rows y0-1..y0+2RY: v 1 + 4/(2RY), f 1 + 2/(2RY) times the compulsory bytes before any L2 reuse
-// (k_tb2 at RY rows per wave: 1 + 4/RY and 1 + 2/RY).
+// (blocks of one y-wave: 1 + 4/RY and 1 + 2/RY).
 // Both y-waves run the same code on a local row index j = -1..RY+1: wave 0 maps j to y0-1+j, wave 1
 // to the mirror image y0+2RY-j, so for both j = 0 is the recomputed halo row, j = 1..RY the own rows,
 // j = RY the row published to the other wave, j = RY+1 the row received from it and j = -1 the one
@@ -3349,19 +2899,17 @@ __global__ __launch_bounds__(WAVE* WXMAX * 2, WPE > 0 ? WPE : 1) void k_tb2y(Coe
     }
 }
 
-// Shapes of the fused pair. Rows of <= 512 points: k_tb2y, 2 y-waves of TBY_RY rows each under the
-// 4 x-waves of a row (8 waves, ~218 VGPRs: two waves per SIMD; NEWTON carries the w rows too and takes
-// 2 rows per wave to stay clear of spills). Rows of <= 1024 points: k_tb2 at 2
-// rows per wave in blocks of <= 8 x-waves (measured on MI355X with tools/kbench.py --pairs: at 2 rows
-// a wave needs ~216 VGPRs, so two waves share a SIMD and hide each other's latency, which beats the
-// lower halo overhead of 3-6 rows at one wave per SIMD by 20-25%).
-constexpr int TBY_RY = 2, TBY_RY_NEWTON = 2, TBY_WX = 4, TB_RY_B = 2, TB_WX_B = 8;
+// Shape of the fused pair: k_tb2y, 2 y-waves of TBY_RY rows each under the 4 x-waves of a row or of a
+// 512-point column block (8 waves, ~218 VGPRs: two waves per SIMD; NEWTON carries the w rows too and takes
+// 2 rows per wave to stay clear of spills; measured on MI355X with tools/kbench.py --pairs: two waves
+// that share a SIMD and hide each other's latency beat the lower halo overhead of 3-6 rows at one wave
+// per SIMD by 20-25%).
+constexpr int TBY_RY = 2, TBY_RY_NEWTON = 2, TBY_WX = 4;
 // prefetch distance of k_tb2y (plane steps): LINEAR keeps two steps in flight (215 VGPRs, still two
 // waves per SIMD; 0.662 vs 0.673 ms per 512^3 pair, profiles/r01m_summary.md), the other modes and
 // the fused prolongation one (VGPR budget: the LINEAR prolongation pair at distance 2 spills)
 constexpr int tby_pfd(int mode) { return mode == GS_LINEAR ? 2 : 1; }
-// column blocks (XH): LINEAR at distance 2 too (247 VGPRs, no spill); GS_TBX_PFD=1 selects distance 1 (A/B)
-bool tbx_pfd2() { return kKnobs.tbxPfd2; }
+// column blocks (XH): LINEAR with a real input iterate at distance 2 too (247 VGPRs, no spill)
 
 // The fused triple ("tb3y"): three LINEAR sweeps per pass in k_tb2y's whole-row tile (4 x-waves x 2 mirrored y-waves
 // x TBY_RY rows, one 8-wave block per CU, XCD-aware tile order, z-chunks of tb2_plan). At plane step z a block
@@ -3693,15 +3241,6 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
     }
 }
 
-// Column blocks (k_tb2y XH) for rows of more than 512 points in LINEAR / NONLINEAR mode: 1024-point rows
-// (BASELINE config #5) were k_tb2's one-y-wave shape before; GS_PAIR_XH=0 restores that (A/B).
-bool xh_enabled() { return kKnobs.pairXh; }
-
-// Geometry rule of the fused pair: the whole x-row in one block (or, XH, one column block of 512
-// points) and enough work for >= 128 blocks of 4-plane chunks; the z-chunk is then chosen for >= 1024
-// blocks (4..64 planes: at 512^3, 64-plane chunks measured 5-8% faster than 32 — fewer re-read
-// chunk-boundary planes). Returns 0 (impossible), 1 (possible) or 2 (possible and fills the GPU);
-// *y2: the k_tb2y whole-row shape, *xh: the k_tb2y column-block shape (neither: k_tb2).
 // Blocks of `threads` threads kernel `fn` keeps resident on the whole GPU (occupancy x CUs, cached).
 int64_t resident_blocks(const void* fn, int threads)
 {
@@ -3770,27 +3309,23 @@ int64_t device_cus()
     return cache[dev] = cus;
 }
 
-// chunk length (planes) of pair launches over plane ranges past a slab's first plane; 0: the rules
-// for whole levels (A/B: GS_SLAB_ZC)
-int slab_zc() { return kKnobs.slabZc; }
-
-// the same for plane ranges from a level's first plane (whole single-GPU levels of >= 2^26 points); A/B
-int whole_zc() { return kKnobs.pairZc; }
-
+// Geometry rule of the fused pair: the whole x-row in one block (or, XH, one column block of 512
+// points) and enough work for >= 128 blocks of 4-plane chunks; the z-chunk is then chosen for >= 1024
+// blocks (4..64 planes: at 512^3, 64-plane chunks measured 5-8% faster than 32 — fewer re-read
+// chunk-boundary planes). Returns 0 (impossible), 1 (possible) or 2 (possible and fills the GPU);
+// *y2: the k_tb2y whole-row shape, *xh: the k_tb2y column-block shape (rows of more than 512 points, up to
+// 2^20; always one of the two).
 int tb2_plan(const gs_stencil* S, const gs_level* L, int* zc, dim3* grid, dim3* block, bool* y2 = nullptr,
-             int mode = GS_LINEAR, bool* xh = nullptr, bool pro = false)
+             int mode = GS_LINEAR, bool* xh = nullptr)
 {
     if (!S || !L || !canonical_order(S) || L->nx < 1 || L->ny < 1 || L->nz < 1) return 0;
     const bool two = L->nx <= 2 * WAVE * TBY_WX;
-    // NEWTON: column blocks from 513 points too since r04 (sweep 2's rows in LDS, edge values loaded per
-    // step: 255 VGPRs, no spill): 1023^3 pair 8.83 vs 29.9 ms for k_tb2, Newton iteration 109-110 vs
-    // 166-167 ms (profiles/r04/r04i_newton_1023.txt); GS_NEWTON_XH=0 keeps k_tb2 for the plain pairs (A/B).
-    // NEWTON prolongation pairs (pro) have no k_tb2 form
-    const bool colb = !two && xh_enabled() && L->nx <= (int64_t)1 << 20 &&
-                      (!newtonish(mode) || pro || kKnobs.newtonXh || L->nx > 2 * WAVE * TB_WX_B);
-    if (!two && !colb && L->nx > 2 * WAVE * TB_WX_B) return 0;
+    // longer rows: column blocks in every mode (NEWTON since r04: sweep 2's rows in LDS, edge values loaded
+    // per step: 255 VGPRs, no spill; profiles/r04/r04i_newton_1023.txt)
+    const bool colb = !two;
+    if (colb && L->nx > (int64_t)1 << 20) return 0;
     const int64_t nh = colb ? (L->nx + 2 * WAVE * TBY_WX - 1) / (2 * WAVE * TBY_WX) : 1;
-    const int rows = (two || colb) ? 2 * (newtonish(mode) ? TBY_RY_NEWTON : TBY_RY) : TB_RY_B; // output rows per block
+    const int rows = 2 * (newtonish(mode) ? TBY_RY_NEWTON : TBY_RY); // output rows per block
     const int64_t tiles = (L->ny + rows - 1) / rows * nh;
     // the block count (of 4-plane chunks) from which the pair is the level's smoother: 128 takes 64^3
     // (256 blocks: ZV pair + prolongation pair 23.5 us vs 4 one-point sweeps + prolongation 24.7 us) and
@@ -3805,7 +3340,6 @@ int tb2_plan(const gs_stencil* S, const gs_level* L, int* zc, dim3* grid, dim3* 
     // rounds at 512^3; fewer re-read chunk-boundary planes): 0.658 vs 0.674 ms per 512^3 pair
     // (tools/kbench.py --pairs --zc 64,96,128). GS_PAIR_BIG_CHUNKS=0 keeps the 64-plane rule (A/B).
     const bool big_chunks = kKnobs.bigChunks;
-    // (k_tb2, 1024-point rows: 5.99 vs 6.12 ms per 1024^3 pair, 0.774 vs 0.779 ms on a 1024x1024x128 slab)
     if (big_chunks && L->nx * L->ny * L->nz >= ((int64_t)1 << 26)) {
         const int64_t b = tiles * L->nz / 512;
         c = b < 64 ? 64 : (b > 128 ? 128 : b);
@@ -3819,7 +3353,7 @@ int tb2_plan(const gs_stencil* S, const gs_level* L, int* zc, dim3* grid, dim3* 
         // GS_PAIR_ONE_ROUND=0 keeps the rule above (A/B).
         const bool one_round = kKnobs.oneRound;
         const int64_t cus = device_cus();
-        if (one_round && (two || colb) && tiles <= cus && L->z0 == 0) {
+        if (one_round && tiles <= cus && L->z0 == 0) {
             const int64_t per = cus / tiles; // chunks per tile
             int64_t c1 = (L->nz + per - 1) / per;
             c1 += c1 & 1;
@@ -3835,31 +3369,16 @@ int tb2_plan(const gs_stencil* S, const gs_level* L, int* zc, dim3* grid, dim3* 
         }
         // plane ranges past a slab's first plane (the interior launch of an overlapped Z-slab sweep):
         // GS_SLAB_ZC-plane chunks, so that blocks retire often and the ghost exchange's kernels
-        // (RCCL's need a whole SIMD's registers) find a free CU soon after they are enqueued
-        if (L->z0 != 0) {
-            const int sz = slab_zc();
-            if (sz > 0) c = std::max(2, sz); // >= 2: the even rounding below must not reach 0
-        } else {
-            const int wz = whole_zc();
-            if (wz > 0) c = std::max(2, wz);
-        }
+        // (RCCL's need a whole SIMD's registers) find a free CU soon after they are enqueued; GS_PAIR_ZC: the
+        // same for plane ranges from a level's first plane (A/B)
+        const int fz = L->z0 != 0 ? kKnobs.slabZc : kKnobs.pairZc;
+        if (fz > 0) c = std::max(2, fz); // >= 2: the even rounding below must not reach 0
     }
     if (kKnobs.midZc > 0 && L->z0 == 0 && L->nx * L->ny * L->nz < ((int64_t)1 << 26)) c = std::max(2, kKnobs.midZc);
-    // GS_PAIR_ONE_ROUND_MID=1: LINEAR levels of 2^24 .. 2^26 points (256^3) in one round of blocks too (A/B)
-    if (kKnobs.oneRoundMid && mode == GS_LINEAR && (two || colb) && L->z0 == 0 &&
-        L->nx * L->ny * L->nz >= ((int64_t)1 << 24) && L->nx * L->ny * L->nz < ((int64_t)1 << 26)) {
-        const int64_t cus = device_cus();
-        if (tiles <= cus) {
-            const int64_t per = cus / tiles;
-            int64_t c1 = (L->nz + per - 1) / per;
-            c1 += c1 & 1;
-            if (c1 > c) c = c1;
-        }
-    }
     c &= ~(int64_t)1; // even: every chunk starts on an odd plane (the fused prolongation's parities)
     *zc = (int)c;
     *grid = dim3((unsigned)tiles, (unsigned)((L->nz + c - 1) / c));
-    *block = dim3(WAVE, colb ? (unsigned)TBY_WX : (unsigned)((L->nx + 2 * WAVE - 1) / (2 * WAVE)), (two || colb) ? 2 : 1);
+    *block = dim3(WAVE, colb ? (unsigned)TBY_WX : (unsigned)((L->nx + 2 * WAVE - 1) / (2 * WAVE)), 2);
     if (y2) *y2 = two;
     if (xh) *xh = colb;
     return fills;

@@ -642,13 +642,8 @@ struct PairVariant {
     void (*kern)(Coef, const double*, const double*, const double*, double*, double*, int, int, int, int64_t,
                  int64_t, int, int, int, const double*, const double*, int, int, int, int64_t, int64_t, const double*);
 };
-#define GS_PV(RY, WX) {"tb2 ry" #RY " wx" #WX, RY, WX, 1, k_tb2<GS_LINEAR, RY, WX, true>}
-#define GS_PVF(RY, WX) {"tb2 ry" #RY " wx" #WX " f-cached", RY, WX, 1, k_tb2<GS_LINEAR, RY, WX, true, false>}
 #define GS_PVY(RY, NTF, SPEC, TAG) {"tb2y ry" #RY " wx4 wy2" TAG, RY, 4, 2, k_tb2y<GS_LINEAR, RY, 4, true, NTF, false, SPEC>}
-const PairVariant kPairVariants[] = {GS_PVF(2, 4),
-                                     GS_PVF(2, 8),
-                                     GS_PV(2, 4),
-                                     GS_PVY(2, false, false, " f-cached"),
+const PairVariant kPairVariants[] = {GS_PVY(2, false, false, " f-cached"),
                                      GS_PVY(3, false, false, " f-cached"),
                                      GS_PVY(2, false, true, " f-cached spec"),
                                      GS_PVY(3, false, true, " f-cached spec"),
@@ -658,8 +653,6 @@ const PairVariant kPairVariants[] = {GS_PVF(2, 4),
                                      {"tb2y ry2 wx4 wy2 f-nt spec pfd2", 2, 4, 2,
                                       k_tb2y<GS_LINEAR, 2, 4, true, true, false, true, 0, 2>}};
 #undef GS_PVY
-#undef GS_PVF
-#undef GS_PV
 constexpr int kNumPairVariants = (int)(sizeof(kPairVariants) / sizeof(kPairVariants[0]));
 
 int gs_debug_num_pair_variants(void) { return kNumPairVariants; }

@@ -88,8 +88,7 @@ const char* gs_jacobi_sweep2_kernel(const gs_stencil* S, const gs_level* L, int 
     mode = base_mode(mode);
     if (bad_level(L) || !valid_stencil(S) || !tb2_plan(S, L, &zc, &g, &b, &y2, mode, &xh)) return "";
     if (y2) return "k_tb2y: 4x2 waves, 2 rows per wave, LDS halo-row exchange, per-wave-row code";
-    if (xh) return "k_tb2y XH: 512-point column blocks of 4x2 waves, edge columns computed lane-parallel";
-    return "k_tb2: <= 8 x-waves, 2 rows per wave";
+    return "k_tb2y XH: 512-point column blocks of 4x2 waves, edge columns computed lane-parallel";
 }
 
 int64_t gs_jacobi_sweep2_num_partials(const gs_stencil* S, const gs_level* L, int mode)
@@ -126,19 +125,14 @@ int gs_jacobi_sweep2_norm_w(const gs_stencil* S, const gs_level* L, int mode, co
         return GS_EINVAL;
     const Coef k = make_coef_w(S, L, omegas, 2, gamma, bconst);
     const int nx = (int)L->nx, ny = (int)L->ny, nz = (int)L->nz;
-#define GS_TB(M, Z) hipLaunchKernelGGL((k_tb2<M, TB_RY_B, TB_WX_B, true, false, Z>), g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0, zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr)
     // LINEAR zero-iterate pairs (the first sweep of a coarse level, v = 0: the lightest variant, three
     // blocks per CU) below 2^26 points: chunks fitted to whole rounds of resident blocks (256^3: 61 vs
     // 71 us; the same rule measured no better for the other pairs, worse for k_rr2 and for NEWTON's
     // zero-iterate pair at two blocks per CU: 133 vs 120 us, r02 tools/fit_session.sh)
     const bool refit = !v_in && !partials && (int64_t)L->nx * L->ny * L->nz < ((int64_t)1 << 26);
-    // GS_SPEC_CACHED=1: pairs with norm partials (the V-cycle's speculative pre-smoothing pair, which k_rr2 reads
-    // next, last planes first) store through the caches instead of non-temporally (A/B)
-    const bool cached = partials && kKnobs.specCached;
 #define GS_TBY2(M, Z, U, P) do { \
         if (refit && M == GS_LINEAR) refit_chunks(&k_tb2y<M, newtonish(M) ? TBY_RY_NEWTON : TBY_RY, TBY_WX, true, false, Z, true, 0, P, false, U>, (int)(b.x * b.y * b.z), nz, 4, 64, true, 2.0, &zc, &g); \
-        if (cached) hipLaunchKernelGGL((k_tb2y<M, newtonish(M) ? TBY_RY_NEWTON : TBY_RY, TBY_WX, false, false, Z, true, 0, P, false, U>), g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0, zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr); \
-        else hipLaunchKernelGGL((k_tb2y<M, newtonish(M) ? TBY_RY_NEWTON : TBY_RY, TBY_WX, true, false, Z, true, 0, P, false, U>), g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0, zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr); } while (0)
+        hipLaunchKernelGGL((k_tb2y<M, newtonish(M) ? TBY_RY_NEWTON : TBY_RY, TBY_WX, true, false, Z, true, 0, P, false, U>), g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0, zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr); } while (0)
 #define GS_TBY1(M, Z, U) GS_TBY2(M, Z, U, tby_pfd(M))
 #define GS_TBY(M, Z) do { if (k.unit) GS_TBY1(M, Z, true); else GS_TBY1(M, Z, false); } while (0)
 #define GS_TBX1(M, Z, P, U) hipLaunchKernelGGL((k_tb2y<M, TBY_RY, TBY_WX, true, false, Z, true, 0, P, true, U>), g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0, zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr)
@@ -147,34 +141,29 @@ int gs_jacobi_sweep2_norm_w(const gs_stencil* S, const gs_level* L, int mode, co
     // FX (r06): LINEAR plain pairs over rows of whole 128-point waves (512-point column blocks) take the instance
     // without per-lane range selects (k_tb2y FX; GS_PAIR_FX=0: the general instance, A/B)
     if (mode == GS_LINEAR && !zv && k.unit && kKnobs.pairFx &&
-        ((xh && tbx_pfd2() && nx % (2 * WAVE * TBY_WX) == 0) || (y2 && nx % (2 * WAVE) == 0))) {
+        ((xh && nx % (2 * WAVE * TBY_WX) == 0) || (y2 && nx % (2 * WAVE) == 0))) {
         if (xh)
             hipLaunchKernelGGL((k_tb2y<GS_LINEAR, TBY_RY, TBY_WX, true, false, false, true, 0, 2, true, true, false, 0, true>),
-                               g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0,
-                               zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr);
-        else if (cached)
-            hipLaunchKernelGGL((k_tb2y<GS_LINEAR, TBY_RY, TBY_WX, false, false, false, true, 0, 2, false, true, false, 0, true>),
                                g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0,
                                zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr);
         else
             hipLaunchKernelGGL((k_tb2y<GS_LINEAR, TBY_RY, TBY_WX, true, false, false, true, 0, 2, false, true, false, 0, true>),
                                g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0,
                                zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr);
-    } else if (mode == GS_NEWTON_B && !zv && y2 && !cached && k.unit && kKnobs.pairFx && nx % (2 * WAVE) == 0) {
+    } else if (mode == GS_NEWTON_B && !zv && y2 && k.unit && kKnobs.pairFx && nx % (2 * WAVE) == 0) {
         hipLaunchKernelGGL((k_tb2y<GS_NEWTON_B, TBY_RY_NEWTON, TBY_WX, true, false, false, true, 0, 1, false, true, false, 0, true>),
                            g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0,
                            zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr);
     } else if (xh) {
         if (mode == GS_LINEAR) {
             if (zv) GS_TBX(GS_LINEAR, true, 1);
-            else if (tbx_pfd2()) GS_TBX(GS_LINEAR, false, 2);
-            else GS_TBX(GS_LINEAR, false, 1);
+            else GS_TBX(GS_LINEAR, false, 2);
         } else if (mode == GS_NONLINEAR) GS_TBX(GS_NONLINEAR, false, 1);
         else if (mode == GS_NEWTON_B && zv) GS_TBX(GS_NEWTON_B, true, 1);
         else if (mode == GS_NEWTON_B) GS_TBX(GS_NEWTON_B, false, 1);
         else if (zv) GS_TBX(GS_NEWTON, true, 1);
         else GS_TBX(GS_NEWTON, false, 1);
-    } else if (y2) {
+    } else {
         if (mode == GS_LINEAR) {
             if (zv) GS_TBY(GS_LINEAR, true);
             else GS_TBY(GS_LINEAR, false);
@@ -183,22 +172,12 @@ int gs_jacobi_sweep2_norm_w(const gs_stencil* S, const gs_level* L, int mode, co
         else if (mode == GS_NEWTON_B) GS_TBY(GS_NEWTON_B, false);
         else if (zv) GS_TBY(GS_NEWTON, true);
         else GS_TBY(GS_NEWTON, false);
-    } else {
-        if (mode == GS_LINEAR) {
-            if (zv) GS_TB(GS_LINEAR, true);
-            else GS_TB(GS_LINEAR, false);
-        } else if (mode == GS_NONLINEAR) GS_TB(GS_NONLINEAR, false);
-        else if (mode == GS_NEWTON_B && zv) GS_TB(GS_NEWTON_B, true);
-        else if (mode == GS_NEWTON_B) GS_TB(GS_NEWTON_B, false);
-        else if (zv) GS_TB(GS_NEWTON, true);
-        else GS_TB(GS_NEWTON, false);
     }
 #undef GS_TBX
 #undef GS_TBX1
 #undef GS_TBY
 #undef GS_TBY1
 #undef GS_TBY2
-#undef GS_TB
     return launch_status();
 }
 
@@ -260,7 +239,7 @@ int gs_jacobi_sweep2_prolong_supported(const gs_stencil* S, const gs_level* L, i
     // columns). The fine planes' parities must be the global ones (even z0): they select each plane's
     // combination
     return !bad_level(L) && valid_stencil(S) && (mode == GS_LINEAR || newtonish(mode)) && L->z0 % 2 == 0 &&
-           tb2_plan(S, L, &zc, &g, &b, &y2, mode, &xh, true) && (y2 || xh);
+           tb2_plan(S, L, &zc, &g, &b, &y2, mode, &xh) && (y2 || xh);
 }
 
 int64_t gs_jacobi_sweep2_prolong_ws_elems(const gs_stencil* S, const gs_level* L, int mode)
@@ -269,7 +248,7 @@ int64_t gs_jacobi_sweep2_prolong_ws_elems(const gs_stencil* S, const gs_level* L
     dim3 g, b;
     bool y2 = false, xh = false;
     mode = base_mode(mode);
-    if (!gs_jacobi_sweep2_prolong_supported(S, L, mode) || !tb2_plan(S, L, &zc, &g, &b, &y2, mode, &xh, true) || !xh)
+    if (!gs_jacobi_sweep2_prolong_supported(S, L, mode) || !tb2_plan(S, L, &zc, &g, &b, &y2, mode, &xh) || !xh)
         return 0;
     const int64_t bw = 2 * WAVE * TBY_WX, nb = (L->nx + bw - 1) / bw - 1; // interior block boundaries
     return nb * (L->nz + 4) * 4 * (L->ny + 2);
@@ -317,7 +296,7 @@ int gs_jacobi_sweep2_prolong_ws_w(const gs_stencil* S, const gs_level* L, int mo
     if (!omegas || !gs_jacobi_sweep2_prolong_supported(S, L, mode) || bad_level(cl) || czoff < 0 || !v_in ||
         !coarse_v || !v_out || !f || v_in == v_out || (mode == GS_NONLINEAR) != (coarse_sub != nullptr) || (newtonish(mode) && !w) ||
         (L->nx + 1) / 2 > cl->nx + 1 || (L->ny + 1) / 2 > cl->ny + 1 || (L->nz + 1) / 2 + czoff > cl->nz + 1 ||
-        !tb2_plan(S, L, &zc, &g, &b, &y2, mode, &xh, true))
+        !tb2_plan(S, L, &zc, &g, &b, &y2, mode, &xh))
         return GS_EINVAL;
     const int64_t need = gs_jacobi_sweep2_prolong_ws_elems(S, L, mode);
     if (need > 0 && (!ws || ws_elems < need)) return GS_EINVAL;
@@ -508,77 +487,6 @@ int gs_residual_restrict_slab(const gs_stencil* S, const gs_level* fl, int mode,
     const bool ldsOnly = kKnobs.rrLds; // A/B switch for tools/ measurements
     const bool rr2 = !ldsOnly && canonical_order(S) && zoff == 0 && wxs <= RR2_WXMAX;
     if (zhi && !rr2) return GS_EINVAL; // the slab form exists for the register kernel only
-    // the LDS-DMA ring form (k_rr2d): rows of up to 4 x-waves (fine rows <= 512 points) whose lanes never clamp a
-    // column (every lane's dwordx4 lies inside the padded row). GS_RR_DMA: 0 never (default), 1 the factor-loading
-    // GS_NEWTON_B launches only, 2 every eligible launch (A/B). Measured slower where it matters (r06):
-    // alone, 512^3 LINEAR 0.533-0.540 vs 0.459 ms, NEWTON_B 0.710-0.712 vs 0.726 ms, GS_NEWTON_G 0.576 vs 0.494 ms;
-    // in the Newton cycle (GS_RR_DMA=1) 29.26 / 29.40 vs 28.58 / 28.55 ms per iteration. One block per CU (the ring
-    // takes 132-144 KB) and LDS-DMA's landing rate, ~25-32 GB/s per CU measured here (MI355X_MICROARCH.md
-    // 'ldsdma-fill': ~25 GB/s per CU), cap it below what two register-loading blocks per CU reach
-    const bool dmaMode = kKnobs.rrDma >= 2 || (kKnobs.rrDma == 1 && mode == GS_NEWTON_B && !bconst);
-    const bool dma = rr2 && dmaMode && wxs <= RR2D_WXMAX && 2 * WAVE * wxs - 1 <= fl->nx + 1;
-    if (dma) {
-        const bool big = fl->nx * fl->ny * fl->nz >= ((int64_t)1 << RR2_NR2_LOG2_POINTS);
-        const int nr_env = kKnobs.rrNr;
-        const int nr = mode == GS_LINEAR && (nr_env == 2 || (nr_env == 0 && big)) ? 2 : 1;
-        const bool wr = newtonish(mode) && !bconst;
-        const int rr = 2 * nr + 1;
-        const int rrows = rr * (wr ? 3 : 2) + 2;
-        const size_t lds = sizeof(double) * ((size_t)RR2D_SLOTS * rrows * wxs * 2 * WAVE +
-                                             (size_t)3 * (RR2D_WXMAX + 2) * rr * 2);
-        const int64_t rows = (cl->ny + nr - 1) / nr;
-        const void* fn = nullptr;
-#define GS_RR2D_FN(M, N, U, W) fn = (const void*)&k_rr2d<M, N, U, W>
-#define GS_RR2D_U(M, N, W) do { if (k.unit) GS_RR2D_FN(M, N, true, W); else GS_RR2D_FN(M, N, false, W); } while (0)
-        if (mode == GS_LINEAR && nr == 2) GS_RR2D_U(GS_LINEAR, 2, false);
-        else if (mode == GS_LINEAR) GS_RR2D_U(GS_LINEAR, 1, false);
-        else if (mode == GS_NEWTON_B && wr) GS_RR2D_U(GS_NEWTON_B, 1, true);
-        else if (mode == GS_NEWTON_B) GS_RR2D_U(GS_NEWTON_B, 1, false);
-        else if (mode == GS_NONLINEAR) GS_RR2D_U(GS_NONLINEAR, 1, false);
-        else GS_RR2D_U(GS_NEWTON, 1, true);
-#undef GS_RR2D_U
-#undef GS_RR2D_FN
-        static std::mutex m;
-        static std::map<std::pair<const void*, size_t>, int64_t> cap;
-        int64_t resident = 0;
-        {
-            std::lock_guard<std::mutex> lk(m);
-            const auto key = std::make_pair(fn, lds);
-            auto it = cap.find(key);
-            if (it == cap.end()) {
-                int per = 0;
-                if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, (int)(WAVE * wxs), lds) != hipSuccess)
-                    per = 0;
-                (void)hipGetLastError();
-                it = cap.emplace(key, per * device_cus()).first;
-            }
-            resident = it->second;
-        }
-        if (resident > 0) {
-            // one round of resident blocks: z-chunks so that rows x chunks ~ the blocks the GPU holds at once
-            const int64_t chunks = std::max<int64_t>(1, resident / rows);
-            int64_t zc = (cl->nz + chunks - 1) / chunks;
-            zc = zc < 1 ? 1 : zc;
-            if (kKnobs.rrZcBig > 0 && big) zc = kKnobs.rrZcBig;
-            if (kKnobs.rrZc > 0 && !big) zc = kKnobs.rrZc;
-            const dim3 g((unsigned)rows, (unsigned)((cl->nz + zc - 1) / zc)), b(WAVE, (unsigned)wxs);
-            Coef ka = k;
-            const double *va = v, *fa = f, *wa = w;
-            double *caa = ca, *cba = cb;
-            int fnx = (int)fl->nx, fny = (int)fl->ny, fnz = (int)fl->nz, cnx = (int)cl->nx, cny = (int)cl->ny,
-                cnz = (int)cl->nz, zca = (int)zc, zha = zhi ? 1 : 0;
-            int64_t fldy = fl->ldy, fldz = fl->ldz, cldy = cl->ldy, cldz = cl->ldz;
-            void* args[] = {&ka, &va, &fa, &wa, &caa, &cba, &fnx, &fny, &fnz, &fldy, &fldz,
-                            &cnx, &cny, &cnz, &cldy, &cldz, &zca, &zha};
-            const hipError_t e = hipLaunchKernel(fn, g, b, args, lds, st);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                return (int)e;
-            }
-            return launch_status();
-        }
-    }
     if (rr2) {
         // >= 2048 blocks of one coarse row where the level has them (chunks of <= 32 coarse planes)
         // LINEAR levels of >= 2^26 points: two coarse rows per block (231 VGPRs, 2 waves per SIMD): 0.507 vs
@@ -588,13 +496,7 @@ int gs_residual_restrict_slab(const gs_stencil* S, const gs_level* fl, int mode,
         const bool big = fl->nx * fl->ny * fl->nz >= ((int64_t)1 << RR2_NR2_LOG2_POINTS);
         // (NEWTON with two rows spills 19 VGPRs: 40.5 vs 38.9 ms per 512^3 Newton iteration, gpurun_out/rrn)
         const int nr = mode == GS_LINEAR && (nr_env == 2 || (nr_env == 0 && big)) ? 2 : 1;
-        // groups of coarse rows per block (k_rr2 NG; GS_RR_NG=2 where the rows fit twice in a block, A/B): two
-        // y-neighbour rows in one 8-wave block cut the 512^3 launch's PMC reads from 1.139 to 1.089 x algorithmic
-        // (NEWTON 1.157 -> 1.087) but run slower — k_rr2 0.479-0.512 vs 0.406-0.453 ms, V-cycle 2.111 vs
-        // 2.055-2.065 ms, Newton 33.4-33.9 vs 32.8-33.4 ms (r05b, interleaved): two 4-wave blocks per CU at their
-        // own barrier phases hide more latency than the halo rows the shared block saves; default one group
-        const int ng = (kKnobs.rrNg == 2 && 2 * wxs <= RR2_WXMAX) ? 2 : 1;
-        const int64_t rows = (cl->ny + nr * ng - 1) / (nr * ng); // blocks along y
+        const int64_t rows = (cl->ny + nr - 1) / nr; // blocks along y
         const int64_t chunks = (2048 + rows - 1) / rows;
         int64_t zc = (cl->nz + chunks - 1) / chunks;
         zc = zc < 1 ? 1 : (zc > 32 ? 32 : zc);
@@ -604,18 +506,10 @@ int gs_residual_restrict_slab(const gs_stencil* S, const gs_level* fl, int mode,
         if (big) zc = cl->nz < 64 ? (cl->nz < 1 ? 1 : cl->nz) : 64;
         if (kKnobs.rrZc > 0 && !big) zc = kKnobs.rrZc;       // (A/B: fine levels of < 2^26 points)
         if (kKnobs.rrZcBig > 0 && big) zc = kKnobs.rrZcBig; // (A/B: fine levels of >= 2^26 points)
-        const dim3 g((unsigned)rows, (unsigned)((cl->nz + zc - 1) / zc)), b(WAVE, (unsigned)wxs, (unsigned)ng);
-        // one operand slot (154 VGPRs, 3 waves per SIMD) measured 1.5 % (level 0) to 9 % (level 1) faster
-        // than the two-slot prefetch ring (228 VGPRs, 2 waves per SIMD): tools/ab_session.sh, ab5
-        // two-row blocks: the rows no neighbouring block reads are non-temporal loads (0.490 vs 0.505 ms at
-        // 512^3, r02 tools/rr_ab_session.sh rrntu); since r05 one-row blocks too (their middle row's f and w: NEWTON_B
-        // level 0 and the LINEAR levels below 2^26 points; Newton iteration 27.73-27.76 vs 27.86-27.97 ms, V-cycle
-        // 2.097-2.100 vs 2.101-2.108 ms, r05w); GS_RR_NTU=0 keeps them cached, =1 restores the two-row-only rule (A/B)
-        const int ntu_env = kKnobs.rrNtu;
-        const bool ntu = ntu_env == 2 || (ntu_env == 1 && nr == 2);
-#define GS_RR2G(M, N, U, T, G) hipLaunchKernelGGL((k_rr2<M, false, N, U, T, G>), g, b, 0, st, k, v, f, w, ca, cb, (int)fl->nx, (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz, (int)zc, zhi ? 1 : 0, kKnobs.rrReverse)
-#define GS_RR2V(M, N, U, T) do { if (ng == 2) GS_RR2G(M, N, U, T, 2); else GS_RR2G(M, N, U, T, 1); } while (0)
-#define GS_RR2U(M, N, U) do { if (ntu) GS_RR2V(M, N, U, true); else GS_RR2V(M, N, U, false); } while (0)
+        const dim3 g((unsigned)rows, (unsigned)((cl->nz + zc - 1) / zc)), b(WAVE, (unsigned)wxs);
+        // (the kernel's one operand slot and its non-temporal loads of the rows no neighbouring block reads: the
+        // measured choices)
+#define GS_RR2U(M, N, U) hipLaunchKernelGGL((k_rr2<M, N, U>), g, b, 0, st, k, v, f, w, ca, cb, (int)fl->nx, (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz, (int)zc, zhi ? 1 : 0, kKnobs.rrReverse)
 #define GS_RR2(M, N) do { if (k.unit) GS_RR2U(M, N, true); else GS_RR2U(M, N, false); } while (0)
         if (mode == GS_LINEAR && nr == 2) GS_RR2(GS_LINEAR, 2);
         else if (mode == GS_LINEAR) GS_RR2(GS_LINEAR, 1);
@@ -624,8 +518,6 @@ int gs_residual_restrict_slab(const gs_stencil* S, const gs_level* fl, int mode,
         else GS_RR2(GS_NEWTON, 1);
 #undef GS_RR2
 #undef GS_RR2U
-#undef GS_RR2V
-#undef GS_RR2G
         return launch_status();
     }
     StencilOffsets so;

@@ -133,8 +133,8 @@ int gs_jacobi_sweep_norm(const gs_stencil* S, const gs_level* L, int mode, doubl
  * nz+1 and nz+2) of v_in are current; 0 = a level boundary. The x-boundary columns (x = 0 and
  * nx+1) of v_in must be zero, as the reference's are (homogeneous Dirichlet, never written). */
 int gs_jacobi_sweep2_supported(const gs_stencil* S, const gs_level* L);
-/* The same for one mode (rows of more than 512 points: column blocks in LINEAR / NONLINEAR mode, any
- * row length; NEWTON up to 1024 points). gs_jacobi_sweep2_supported is the minimum over the modes. */
+/* The same for one mode (rows of more than 512 points: column blocks in every mode, up to 2^20
+ * points). gs_jacobi_sweep2_supported is the minimum over the modes. */
 int gs_jacobi_sweep2_supported_mode(const gs_stencil* S, const gs_level* L, int mode);
 int gs_jacobi_sweep2(const gs_stencil* S, const gs_level* L, int mode, double omega, double gamma,
                      const double* v_in, double* v_out, const double* f, const double* w, int zlo, int zhi,

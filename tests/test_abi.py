@@ -161,3 +161,57 @@ def test_executable_config_path_quoting_without_gpu(tmp_path):
             assert r.returncode == 1 and r.stderr == "Invalid mode\n", name
             assert r.stdout.splitlines() == case["stdout"][:1], (name, r.stdout)
             (tmp_path / rel_path).unlink()
+
+
+RETIRED_SWITCHES = {"GS_RR_DMA", "GS_RR_NG", "GS_RR_NTU", "GS_PAIR_XH", "GS_NEWTON_XH", "GS_SPEC_CACHED", "GS_TBX_PFD",
+                    "GS_PAIR_ONE_ROUND_MID"}
+
+
+def test_switch_inventory_matches_integration_doc():
+    """The GS_* names the product's sources read from the environment are exactly the ones INTEGRATION.md's
+    tables document, and no retired switch is left in either. A name reaches getenv directly, through
+    Knobs::num, or through one of the three local helpers that forward their argument to getenv (`on` in
+    gs_grid.cpp, envInt in gs_main.cpp, commTimeoutS in gs_hostsync.cpp); any other "GS_..." string literal in
+    these files would be a reader this test does not know, so there must be none."""
+    csrc = os.path.join(REPO, "gpu-solve_amd", "csrc")
+    text = "".join(open(os.path.join(csrc, f)).read() for f in (
+        "gs_device.hpp", "gs_kernels.hip", "gs_grid.cpp", "gs_capi.cpp", "gs_comm.cpp", "gs_main.cpp", "gs_hostsync.cpp"))
+    code = set(re.findall(r'\b(?:getenv|num|on|envInt|commTimeoutS)\(\s*"(GS_[A-Z0-9_]+)"', text))
+    assert code == set(re.findall(r'"(GS_[A-Z0-9_]+)"', text))
+    doc = set()
+    for line in open(os.path.join(REPO, "INTEGRATION.md")):
+        if line.startswith("| `GS_"):
+            doc |= set(re.findall(r"`(GS_[A-Z0-9_]+)", line.split("|")[1]))
+    assert code == doc, (sorted(code - doc), sorted(doc - code))
+    assert not (RETIRED_SWITCHES & (code | doc))
+
+
+@pytest.mark.parametrize("general", [False, True])
+def test_pair_plan(general):
+    """The fused pair's plan (tb2_plan through the C ABI; launches nothing, and touches no device below 2^26
+    points): rows of up to 512 points take the whole-row k_tb2y shape, longer rows its 512-point column blocks
+    up to 2^20 points, in every mode and for unit and general stencils; blocks of 4 output rows, one per column
+    block and z-chunk, the chunk being max(4, min(64, tiles * nz / 1024)) made even."""
+    k = gsv.kernels()
+    S = gsv._abi.gs_stencil()
+    S.s[:] = [6.5, -1.0, -1.25, -1.0, -0.75, -1.0, -1.0] if general else [6.0] + [-1.0] * 6
+    S.ox[:], S.oy[:], S.oz[:] = zip(*gsv.CANONICAL_OFFSETS)
+
+    def level(nx, ny, nz):
+        ldy, ldz, _, _ = gsv.field_layout(nx, ny, nz)
+        return gsv._abi.gs_level(nx, ny, nz, ldy, ldz, 0, 1.0 / (ny + 1))
+
+    ny = nz = 6
+    for mode in range(5):
+        for nx in (512, 513, 700, 1024, 1025, 2000):
+            L = level(nx, ny, nz)
+            assert k.gs_jacobi_sweep2_supported_mode(C.byref(S), C.byref(L), mode) >= 1, (mode, nx)
+            name = k.gs_jacobi_sweep2_kernel(C.byref(S), C.byref(L), mode).decode()
+            assert name.startswith("k_tb2y:" if nx == 512 else "k_tb2y XH"), (mode, nx, name)
+            tiles = -(-ny // 4) * -(-nx // 512)
+            zc = max(4, min(64, tiles * nz // 1024)) & ~1
+            assert k.gs_jacobi_sweep2_num_partials(C.byref(S), C.byref(L), mode) == tiles * -(-nz // zc), (mode, nx)
+        L = level(2**20 + 1, ny, nz)
+        assert k.gs_jacobi_sweep2_supported_mode(C.byref(S), C.byref(L), mode) == 0
+        assert k.gs_jacobi_sweep2_kernel(C.byref(S), C.byref(L), mode) == b""
+        assert k.gs_jacobi_sweep2_num_partials(C.byref(S), C.byref(L), mode) == 0

@@ -56,8 +56,7 @@ def two_sweeps(v0, f0, w0, mode, h):
 
 SHAPES = [(1, 1, 1), (2, 5, 3), (5, 4, 33), (127, 9, 17), (128, 8, 8), (129, 13, 40), (257, 6, 10), (500, 7, 9),
           (512, 4, 5), (513, 5, 6), (1024, 3, 4), (64, 64, 64), (200, 33, 70),
-          # rows > 512 points: column blocks (k_tb2y XH) in every mode (NEWTON rows of 513-1024 points since r04;
-          # GS_NEWTON_XH=0 keeps k_tb2 for them, tests/test_gpu_switches.py)
+          # rows > 512 points: column blocks (k_tb2y XH) in every mode
           (700, 9, 11), (1024, 16, 12), (1025, 7, 9), (1536, 5, 6), (2000, 3, 5)]
 
 

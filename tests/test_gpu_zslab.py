@@ -41,8 +41,8 @@ def single(params, sweeps, solve):
 
 @pytest.mark.parametrize("dims,nranks", [((33, 17, 40), 2), ((64, 64, 64), 4), ((31, 20, 61), 3),
                                          ((128, 64, 96), 8),
-                                         # slabs large enough for the fused pairs (k_tb2y; k_tb2 for rows
-                                         # > 512), their depth-2 ghosts and the overlapped boundary planes
+                                         # slabs large enough for the fused pairs (k_tb2y; column blocks for
+                                         # rows > 512), their depth-2 ghosts and the overlapped boundary planes
                                          ((64, 256, 64), 2), ((32, 512, 64), 4), ((600, 128, 64), 2),
                                          ((48, 512, 70), 3)])
 def test_sweeps_bit_identical(dims, nranks):

@@ -23,10 +23,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def sweep_kernel(name):
     """The level-0 smoother of bench.py's headline: the fused LINEAR pair (k_tb2y whole-row shape, not the
-    column blocks of config #5's 1024-point rows, not the prolongation / zero-iterate forms, or k_tb2) or,
+    column blocks of config #5's 1024-point rows, not the prolongation / zero-iterate forms) or,
     without it, the one-sweep k_rb."""
-    if "k_tb2<0," in name:
-        return True
     if "k_tb2y<0," not in name:
         return False
     args = [a.strip() for a in name[name.index("k_tb2y<") + 7:].split(">")[0].split(",")]
