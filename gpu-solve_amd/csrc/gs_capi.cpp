@@ -188,6 +188,19 @@ int gs_grid_set_weights(void* grid, const double* pre, int npre, const double* p
     return guarded([&] { G(grid).setWeights(pre, npre, post, npost); });
 }
 
+int gs_grid_set_transfer(void* grid, int mode)
+{
+    return guarded([&] { G(grid).setTransfer(mode); });
+}
+
+int gs_grid_get_transfer(void* grid) { return G(grid).transferMode; }
+
+int gs_grid_level_aligned(void* grid, int level)
+{
+    if (level < 0 || level + 1 >= (int)G(grid).numLevels()) return -1;
+    return G(grid).levelAligned((std::size_t)level) ? 1 : 0;
+}
+
 int gs_grid_get_weights(void* grid, double* pre, double* post)
 {
     const auto& g = G(grid);

@@ -160,6 +160,9 @@ LevelClock::~LevelClock()
 
 int64_t proWsElems(const HipGridData& g, std::size_t l); // below
 
+static const char* const kTransferSingleGpu =
+    "transfer: POSITION needs a single-GPU grid (not a Z-slab / RCCL or schedule-trace grid)";
+
 // ---------------------------------------------------------------------------------------------
 // Level hierarchy: L = floor(log2(min dim)) + 1, dims halve per level, h_l = 1/(ny_l+1)
 // (src/cpu/CpuGridData.cpp:19-41). Fields a mode never touches are not allocated.
@@ -202,6 +205,15 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
         // GS_OMEGAS: per-sweep relaxation weights; a malformed value or a count mismatch throws here, before any work
         if (const char* e = std::getenv("GS_OMEGAS")) weights = parseOmegas(e, preSmoothing, postSmoothing);
     }
+    // GS_TRANSFER=position|reference: the grid transfers (setTransfer, once the levels exist); anything else throws here
+    int transferEnv = 0;
+    if (const char* e = std::getenv("GS_TRANSFER")) {
+        const std::string t = e;
+        if (t == "position") transferEnv = 1;
+        else if (t != "reference")
+            throw Error("GS_TRANSFER=" + t + ": the value must be position or reference");
+    }
+    if (transferEnv == 1 && (nranks() > 1 || traceLog)) throw Error(kTransferSingleGpu); // before any work or collective
     std::vector<int64_t> nzs, pts;
     for (int l = 0; l < nlev; l++) {
         LevelData& L = levels_[l];
@@ -273,6 +285,8 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
                 coarseFrom = (std::size_t)l;
             }
     }
+    coarseFromRef_ = coarseFrom;
+    xferT_.assign(levels_.size(), gs_transfer_tables{});
     if (mode == NEWTON) newtonF = DeviceField(levels_[0].geom.nx, levels_[0].geom.ny, levels_[0].geom.nz, s, dry);
     newtonVZero_ = mode == NEWTON; // (every field is created zero-filled)
     {
@@ -335,6 +349,74 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
         if (bndStream_.s) levels_[l].proWs[1].get(need);
     }
     check((int)hipStreamSynchronize(s), "hipStreamSynchronize");
+    if (transferEnv) setTransfer(transferEnv);
+}
+
+bool HipGridData::levelAligned(std::size_t l) const
+{
+    if (l + 1 >= levels_.size()) return true;
+    const auto &f = levels_[l].levelDim, &c = levels_[l + 1].levelDim;
+    return f[0] == 2 * c[0] + 1 && f[1] == 2 * c[1] + 1 && f[2] == 2 * c[2] + 1;
+}
+
+void HipGridData::setTransfer(int m)
+{
+    if (m != 0 && m != 1) throw Error("transfer: the mode must be GS_TRANSFER_REFERENCE (0) or GS_TRANSFER_POSITION (1)");
+    if (m == 1 && (nranks() > 1 || trace))
+        throw Error(kTransferSingleGpu);
+    const std::size_t nl = levels_.size();
+    for (std::size_t l = 0; m == 1 && l + 1 < nl; l++) {
+        if (levelAligned(l) || xferT_[l].pj[0]) continue;
+        // one allocation per transition: per axis pj, pt (nf + 2), rlo, rcnt (nc + 2), rw (4 (nc + 2)); the doubles
+        // first, so that every array is 8-byte aligned
+        gs_transfer_tables T{};
+        std::vector<std::vector<int32_t>> pj(3), rlo(3), rcnt(3);
+        std::vector<std::vector<double>> pt(3), rw(3);
+        std::size_t bytes = 0;
+        for (int a = 0; a < 3; a++) {
+            const int64_t nf = (int64_t)levels_[l].levelDim[a], nc = (int64_t)levels_[l + 1].levelDim[a];
+            T.nf[a] = nf;
+            T.nc[a] = nc;
+            pj[a].resize(nf + 2);
+            pt[a].resize(nf + 2);
+            rlo[a].resize(nc + 2);
+            rcnt[a].resize(nc + 2);
+            rw[a].resize(4 * (nc + 2));
+            check(gs_transfer_axis(nf, nc, pj[a].data(), pt[a].data(), rlo[a].data(), rcnt[a].data(), rw[a].data()),
+                  "gs_transfer_axis");
+            bytes += sizeof(double) * (pt[a].size() + rw[a].size()) +
+                     sizeof(int32_t) * (pj[a].size() + rlo[a].size() + rcnt[a].size() + 2);
+        }
+        char* base = nullptr;
+        check((int)hipMalloc((void**)&base, bytes), "hipMalloc(transfer tables)");
+        xferMem_.push_back(base);
+        std::size_t off = 0;
+        auto put = [&](const void* src, std::size_t n) {
+            check((int)hipMemcpy(base + off, src, n, hipMemcpyHostToDevice), "hipMemcpy(transfer tables)");
+            const void* p = base + off;
+            off += n;
+            return p;
+        };
+        for (int a = 0; a < 3; a++) {
+            T.pt[a] = (const double*)put(pt[a].data(), sizeof(double) * pt[a].size());
+            T.rw[a] = (const double*)put(rw[a].data(), sizeof(double) * rw[a].size());
+        }
+        for (int a = 0; a < 3; a++) {
+            T.pj[a] = (const int32_t*)put(pj[a].data(), sizeof(int32_t) * pj[a].size());
+            T.rlo[a] = (const int32_t*)put(rlo[a].data(), sizeof(int32_t) * rlo[a].size());
+            T.rcnt[a] = (const int32_t*)put(rcnt[a].data(), sizeof(int32_t) * rcnt[a].size());
+        }
+        xferT_[l] = T;
+    }
+    transferMode = m;
+    // the one-launch coarse cycle embeds the index-aligned transfers: in POSITION mode it starts at the first level,
+    // from the reference rule's on, below which every transition is aligned (none: no coarse launch)
+    coarseFrom = coarseFromRef_;
+    if (m == 1 && coarseFromRef_ < nl) {
+        std::size_t c = nl - 1;
+        while (c > coarseFromRef_ && levelAligned(c - 1)) c--;
+        coarseFrom = c;
+    }
 }
 
 HipGridData::~HipGridData()
@@ -342,6 +424,7 @@ HipGridData::~HipGridData()
     if (stream_.s) (void)hipStreamSynchronize(stream_.s);
     if (commStream_.s) (void)hipStreamSynchronize(commStream_.s);
     if (bndStream_.s) (void)hipStreamSynchronize(bndStream_.s);
+    for (void* p : xferMem_) (void)hipFree(p);
     if (partials_ && !trace) (void)hipFree(partials_);
     if (dNorm_) (void)hipFree(dNorm_);
     if (dRankSums_) (void)hipFree(dRankSums_);
@@ -713,7 +796,10 @@ void restrictTo(HipGridData& g, const DeviceField& src, std::size_t l, DeviceFie
             g.rec("restrict", {{"L", (long long)l}, {"c1", cg.z0 + 1}, {"c2", cg.z0 + cg.nz}, {"two", b != nullptr}},
                   (std::string(HipGridData::fieldName(F, src)) + ">" + HipGridData::fieldName(C, a) +
                    (b ? std::string(",") + HipGridData::fieldName(C, *b) : std::string())).c_str());
-    } else if (cg.nz > 0)
+    } else if (g.pa(l))
+        check(gs_restrict_pa(src.data(), &F.geom, a.data(), b ? b->data() : nullptr, &C.geom, g.xfer(l), s),
+              "gs_restrict_pa");
+    else if (cg.nz > 0)
         check(gs_restrict2(src.data(), &F.geom, a.data() + off, b ? b->data() + off : nullptr, &cg, s), "gs_restrict");
     if (transitionLevel(g, l + 1)) {
         g.gather(C, a);
@@ -1116,7 +1202,8 @@ void HipSolver::upLeg(HipGridData& grid, std::size_t i)
     materialize(grid, i); // only if the level had no sweep at all
     // (the tiled step fuses the prolongation with a pair: the GS_NO_FUSED_SWEEPS / GS_NO_FUSED_PROLONG
     // alternatives take the general path below)
-    if (i - 1 >= 1 && F.tiled && !C.distributed && grid.postSmoothing >= 2 && grid.sw.fusedSweeps &&
+    const bool pa = grid.pa(i - 1); // position-aware transfers: the general path below, with gs_prolong_add_pa
+    if (!pa && i - 1 >= 1 && F.tiled && !C.distributed && grid.postSmoothing >= 2 && grid.sw.fusedSweeps &&
         grid.sw.fusedProlong) {
         // a small level: prolongation, correction and the first two post-smoothing sweeps in one launch
         materialize(grid, i - 1);
@@ -1136,7 +1223,7 @@ void HipSolver::upLeg(HipGridData& grid, std::size_t i)
         grid.clock.mark(s, (int)(i - 1), false);
         return;
     }
-    if (grid.sw.fusedProlong && F.fusedPairs && grid.postSmoothing >= 2 && proWorthIt(grid, i - 1) && proSlabOk(grid, i - 1) &&
+    if (!pa && grid.sw.fusedProlong && F.fusedPairs && grid.postSmoothing >= 2 && proWorthIt(grid, i - 1) && proSlabOk(grid, i - 1) &&
         gs_jacobi_sweep2_prolong_supported(&grid.stencilAbi, &F.geom, (int)grid.mode)) {
         // the first two post-smoothing sweeps of v^h + P v^2h in one pass (the corrected
         // iterate is never stored), then the remaining ones. On a Z-slab each rank corrects its
@@ -1170,7 +1257,12 @@ void HipSolver::upLeg(HipGridData& grid, std::size_t i)
     // v^h += P (v^2h [- restV^2h])   (CpuSolver.cpp:121-132, interpolate + v += e fused)
     if (grid.trace)
         grid.rec("prolongadd", {{"L", (long long)(i - 1)}, {"sub", grid.mode == GridParams::NONLINEAR}});
-    else
+    else if (pa) {
+        materialize(grid, i - 1);
+        check(gs_prolong_add_pa(C.v.data(), grid.mode == GridParams::NONLINEAR ? C.restV.data() : nullptr, &C.geom,
+                                F.v.data(), &F.geom, grid.xfer(i - 1), s),
+              "gs_prolong_add_pa");
+    } else
         check(gs_prolong_add(C.v.data(), grid.mode == GridParams::NONLINEAR ? C.restV.data() : nullptr, &C.geom,
                              F.v.data(), &F.geom, s),
               "gs_prolong_add");
@@ -1203,7 +1295,8 @@ void HipSolver::downFrom(HipGridData& grid, std::size_t from, int* pending)
         auto& C = grid.getLevel(i + 1);
         // (the tiled step fuses a pair, the residual and the restriction and leaves v^2h = 0 as a flag: the
         // GS_NO_FUSED_SWEEPS / GS_NO_FUSED_RR / GS_NO_ZERO_GUESS alternatives take the general path below)
-        if (i >= 1 && pre == 2 && L.tiled && !C.distributed && grid.sw.fusedSweeps && grid.sw.fusedRR &&
+        const bool pa = grid.pa(i); // position-aware transfers: the general path below with the _pa launchers
+        if (!pa && i >= 1 && pre == 2 && L.tiled && !C.distributed && grid.sw.fusedSweeps && grid.sw.fusedRR &&
             grid.sw.zeroGuess) {
             // a small level: the pre-smoothing pair, residual and restriction in one tiled launch
             if (grid.trace)
@@ -1229,7 +1322,14 @@ void HipSolver::downFrom(HipGridData& grid, std::size_t from, int* pending)
         if (grid.sw.fusedRR) {
             materialize(grid, i);
             const double* w = grid.wOf(L);
-            if (!(L.distributed && grid.nranks() > 1)) {
+            if (pa) {
+                if (HipGridData::paFusedRR) {
+                    check(gs_residual_restrict_pa(&grid.stencilAbi, &L.geom, grid.kmode(), grid.gamma, L.v.data(),
+                                                  L.f.data(), w, C.f.data(), &C.geom, grid.xfer(i), s),
+                          "gs_residual_restrict_pa");
+                    fused = true;
+                }
+            } else if (!(L.distributed && grid.nranks() > 1)) {
                 if (grid.trace)
                     grid.rec("resrestrict", {{"L", (long long)i}, {"c1", 1}, {"c2", C.geom.nz}, {"zhi", 0}});
                 else
@@ -1514,7 +1614,8 @@ double NewtonSolver::compFUpdate(HipGridData& grid)
     auto& L0 = grid.getLevel(0);
     // single GPU: the next findError's restriction of newtonV onto level 1 (NewtonSolver.cpp:88-92) comes out of
     // the same pass (gs_newton_F_update_restrict), so findError skips that 1.1 GB re-read at 512^3
-    const bool r1 = grid.numLevels() >= 3 && !(L0.distributed && grid.nranks() > 1) &&
+    // (gs_newton_F_update_restrict embeds the index-aligned restriction: not where level 0's transition is position-aware)
+    const bool r1 = grid.numLevels() >= 3 && !(L0.distributed && grid.nranks() > 1) && !grid.pa(0) &&
                     (grid.trace || grid.getLevel(1).newtonVNext.data() != nullptr) &&
                     gs_newton_F_update_restrict_supported(&grid.stencilAbi, &L0.geom, &grid.getLevel(1).geom) != 0;
     // the same pass also writes the next inner solve's GS_NEWTON_B factor of level 0 (from the exp(w') compF

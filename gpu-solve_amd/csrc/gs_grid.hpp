@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "gpusolve_hip.h"
+#include "gpusolve_transfer.h"
 #include "gs_comm.hpp"
 #include "gs_params.hpp"
 
@@ -186,6 +187,23 @@ public:
     // counts must equal preSmoothing / postSmoothing and be at most GS_MAX_WEIGHTS, every weight finite;
     // (NULL, 0, NULL, 0) clears. Throws, leaving the weights as they were.
     void setWeights(const double* pre, int npre, const double* post, int npost);
+    // Grid transfers (gs_grid_set_transfer, GS_TRANSFER). 0, the default: the reference's index-aligned restrict /
+    // interpolate on every transition. 1 (POSITION): every transition that is not aligned (fine n = 2 coarse n + 1 on
+    // all three axes) takes the position-aware operators of include/gpusolve_transfer.h through the general path
+    // (sweeps, gs_residual_restrict_pa, gs_restrict_pa, gs_prolong_add_pa, sweeps); the tiled steps, k_rr2, the fused
+    // prolongation pairs and gs_newton_F_update_restrict embed the index-aligned operator and are not taken there,
+    // and the one-launch coarse cycle starts only where every transition below is aligned. Aligned transitions are
+    // unchanged launch for launch. With the other two (GS_FMG, GS_OMEGAS) the switches that change the iterate.
+    int transferMode = 0;
+    // single-GPU grids only; builds and uploads the tables of every non-aligned transition the first time POSITION is
+    // switched on. Throws, leaving the grid as it was.
+    void setTransfer(int mode);
+    bool levelAligned(std::size_t l) const; // the transition l -> l + 1 (l + 1 < numLevels())
+    bool pa(std::size_t l) const { return transferMode == 1 && !levelAligned(l); }
+    const gs_transfer_tables* xfer(std::size_t l) const { return &xferT_[l]; }
+    // where the position-aware path is taken, f^2h = R(f^h - A v^h) in one pass (gs_residual_restrict_pa) rather
+    // than gs_residual with a stored r followed by gs_restrict_pa (DESIGN.md §4.9 has the A/B)
+    static constexpr bool paFusedRR = true;
     // levels coarseFrom .. numLevels()-1 run as ONE gs_coarse_cycle launch in every V-cycle
     // (numLevels(): none); set from GS_COARSE_POINTS at construction
     std::size_t coarseFrom = 0;
@@ -259,6 +277,9 @@ private:
     hipEvent_t evBnd_[2] = {nullptr, nullptr}; // boundary planes of sweep k (k & 1) in a pipelined sequence
     std::vector<double> dryParts_;
     long traceNorms_ = 0;
+    std::size_t coarseFromRef_ = 0;          // coarseFrom of the REFERENCE transfers (GS_COARSE_POINTS' rule)
+    std::vector<gs_transfer_tables> xferT_;  // per transition l -> l + 1; null pointers where aligned or not built
+    std::vector<void*> xferMem_;             // the device allocations behind them
     bool haloPending_ = false; // an exchange issued by haloIssue, not settled
     friend class NewtonSolver;
     bool newtonR1_ = false;    // level 1's newtonVNext holds R(level 0's newtonV) (gs_newton_F_update_restrict)

@@ -1,0 +1,131 @@
+// gs_transfer.hip — libgpusolve_transfer.so: the position-aware grid transfers of include/gpusolve_transfer.h
+// (definitions and evaluation order there). Its own library and header: libgpusolve_hip.so's export list and its
+// kernels stay what they are. gs_device.hpp gives Coef, the residual's point expressions and the launch helpers.
+#include "gs_device.hpp"
+#include "gs_transfer_device.hpp"
+
+#include "gpusolve_transfer.h"
+
+namespace {
+
+bool bad_transfer(const gs_level* fl, const gs_level* cl, const gs_transfer_tables* T)
+{
+    if (bad_level(fl) || bad_level(cl) || !T || fl->z0 != 0 || cl->z0 != 0) return true;
+    const int64_t nf[3] = {fl->nx, fl->ny, fl->nz}, nc[3] = {cl->nx, cl->ny, cl->nz};
+    for (int a = 0; a < 3; a++) {
+        if (nf[a] < 2 || nc[a] != nf[a] / 2 || T->nf[a] != nf[a] || T->nc[a] != nc[a]) return true;
+        if (!T->pj[a] || !T->pt[a] || !T->rlo[a] || !T->rcnt[a] || !T->rw[a]) return true;
+    }
+    // one block per plane (transfers) / per PA_TYC coarse rows: the grid's y and z extents
+    return fl->nz > 65535 || (fl->ny + 3) / 4 > 65535;
+}
+
+PaTables device_tables(const gs_transfer_tables* T)
+{
+    PaTables d;
+    for (int a = 0; a < 3; a++) {
+        d.pj[a] = T->pj[a];
+        d.pt[a] = T->pt[a];
+        d.rlo[a] = T->rlo[a];
+        d.rcnt[a] = T->rcnt[a];
+        d.rw[a] = T->rw[a];
+    }
+    return d;
+}
+
+} // namespace
+
+extern "C" {
+
+int gs_transfer_axis(int64_t nf, int64_t nc, int32_t* pj, double* pt, int32_t* rlo, int32_t* rcnt, double* rw)
+{
+    if (nf < 2 || nf > INT32_MAX / 2 || nc != nf / 2 || !pj || !pt || !rlo || !rcnt || !rw) return GS_EINVAL;
+    const int64_t D = nf + 1;
+    const double s = (double)(nc + 1) / (double)D;
+    for (int64_t J = 0; J <= nc + 1; J++) {
+        rlo[J] = 0;
+        rcnt[J] = 0;
+        for (int k = 0; k < 4; k++) rw[4 * J + k] = 0.0;
+    }
+    pj[0] = pj[nf + 1] = 0;
+    pt[0] = pt[nf + 1] = 0.0;
+    // fine point i feeds coarse pj[i] + 1 (weight s * pt[i], if rem > 0) and coarse pj[i] (weight s * pa[i]): taken in
+    // ascending i, every coarse point's list comes out ascending, its pj = J - 1 points before its pj = J points
+    auto feed = [&](int64_t J, int64_t i, double w) {
+        if (J < 1 || J > nc) return true; // the coarse ring gathers nothing
+        if (rcnt[J] == 0) rlo[J] = (int32_t)i;
+        if (rcnt[J] >= 4 || rlo[J] + rcnt[J] != i) return false;
+        rw[4 * J + rcnt[J]++] = w;
+        return true;
+    };
+    for (int64_t i = 1; i <= nf; i++) {
+        const int64_t q = i * (nc + 1), j = q / D, rem = q % D;
+        pj[i] = (int32_t)j;
+        pt[i] = (double)rem / (double)D;
+        const double pa = 1.0 - pt[i];
+        if (!feed(j, i, s * pa)) return GS_EINVAL;
+        if (rem > 0 && !feed(j + 1, i, s * pt[i])) return GS_EINVAL;
+    }
+    return 0;
+}
+
+int gs_restrict_pa(const double* fine, const gs_level* fl, double* coarse_a, double* coarse_b, const gs_level* cl,
+                   const gs_transfer_tables* T, hipStream_t st)
+{
+    if (!fine || !coarse_a || bad_transfer(fl, cl, T)) return GS_EINVAL;
+    const dim3 g((unsigned)((cl->nx + 63) / 64), (unsigned)((cl->ny + 3) / 4), (unsigned)cl->nz), b(64, 4);
+    hipLaunchKernelGGL(k_restrict_pa, g, b, 0, st, device_tables(T), fine, coarse_a, coarse_b, (int)cl->nx, (int)cl->ny,
+                       (int)fl->nx, (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, cl->ldy, cl->ldz);
+    return launch_status();
+}
+
+int gs_prolong_add_pa(const double* coarse_v, const double* coarse_sub, const gs_level* cl, double* fine_v,
+                      const gs_level* fl, const gs_transfer_tables* T, hipStream_t st)
+{
+    if (!coarse_v || !fine_v || bad_transfer(fl, cl, T)) return GS_EINVAL;
+    const dim3 g((unsigned)((fl->nx + 127) / 128), (unsigned)((fl->ny + 3) / 4), (unsigned)fl->nz), b(64, 4);
+    if (coarse_sub)
+        hipLaunchKernelGGL(k_prolong_add_pa<true>, g, b, 0, st, device_tables(T), coarse_v, coarse_sub, fine_v,
+                           (int)fl->nx, (int)fl->ny, (int)cl->nx, (int)cl->ny, (int)cl->nz, fl->ldy, fl->ldz, cl->ldy,
+                           cl->ldz);
+    else
+        hipLaunchKernelGGL(k_prolong_add_pa<false>, g, b, 0, st, device_tables(T), coarse_v, coarse_sub, fine_v,
+                           (int)fl->nx, (int)fl->ny, (int)cl->nx, (int)cl->ny, (int)cl->nz, fl->ldy, fl->ldz, cl->ldy,
+                           cl->ldz);
+    return launch_status();
+}
+
+int gs_residual_restrict_pa(const gs_stencil* S, const gs_level* fl, int mode, double gamma, const double* v,
+                            const double* f, const double* w, double* coarse_f, const gs_level* cl,
+                            const gs_transfer_tables* T, hipStream_t st)
+{
+    mode = base_mode(mode); // (GS_NEWTON_G: the factor field is read; it holds gamma)
+    if (!S || !valid_stencil(S) || !v || !f || !coarse_f || mode < GS_LINEAR || mode > GS_NEWTON_B ||
+        (newtonish(mode) && !w) || bad_transfer(fl, cl, T))
+        return GS_EINVAL;
+    const Coef k = make_coef(S, fl, 0.0, gamma);
+    PaStencil so;
+    for (int t = 0; t < 7; t++) {
+        so.lds[t] = S->ox[t] + S->oy[t] * PA_VX;
+        so.oz[t] = S->oz[t];
+    }
+    // z-chunks of 4..32 coarse planes, for ~1024 blocks where the level has them
+    const int64_t tiles = ((cl->nx + PA_TXC - 1) / PA_TXC) * ((cl->ny + PA_TYC - 1) / PA_TYC);
+    int64_t zc = cl->nz * tiles / 1024;
+    zc = zc < 4 ? 4 : (zc > 32 ? 32 : zc);
+    const dim3 g((unsigned)((cl->nx + PA_TXC - 1) / PA_TXC), (unsigned)((cl->ny + PA_TYC - 1) / PA_TYC),
+                 (unsigned)((cl->nz + zc - 1) / zc)),
+        b(PA_T);
+#define GS_PA(M)                                                                                                       \
+    hipLaunchKernelGGL((k_resrestrict_pa<M>), g, b, 0, st, k, so, device_tables(T), v, f, w, coarse_f, (int)fl->nx,   \
+                       (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy,     \
+                       cl->ldz, (int)zc)
+    if (mode == GS_LINEAR) GS_PA(GS_LINEAR);
+    else if (mode == GS_NONLINEAR) GS_PA(GS_NONLINEAR);
+    else if (mode == GS_NEWTON_B) GS_PA(GS_NEWTON_B);
+    else GS_PA(GS_NEWTON);
+#undef GS_PA
+    return launch_status();
+}
+
+} // extern "C"

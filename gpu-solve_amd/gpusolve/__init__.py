@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import GS_LINEAR, GS_MAX_WEIGHTS, GS_NEWTON, GS_NEWTON_B, GS_NEWTON_G, GS_NONLINEAR, gs_level, gs_params, gs_stencil, kernels, driver, diag  # noqa: F401
+from ._abi import GS_TRANSFER_POSITION, GS_TRANSFER_REFERENCE, gs_transfer_tables, transfer  # noqa: F401
 
 CANONICAL_OFFSETS = [(0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)]
 
@@ -105,6 +106,7 @@ def _check(rc: int):
         raise GpuSolveError(driver().gs_last_error().decode())
 
 
+_TRANSFERS = {"reference": GS_TRANSFER_REFERENCE, "position": GS_TRANSFER_POSITION}
 FIELDS = {"v": 0, "restV": 1, "newtonV": 2, "f": 3, "r": 4, "newtonF": 5}
 
 
@@ -181,6 +183,29 @@ class HipGridData:
         if not driver().gs_grid_get_weights(self.handle, a, b):
             return None
         return tuple(a[:npre]), tuple(b[:npost])
+
+    def set_transfer(self, mode: str):
+        """The grid transfers of the V-cycle: "reference" (the default: the reference's index-aligned restrict /
+        interpolate on every transition) or "position" (the position-aware operators of include/gpusolve_transfer.h
+        on every transition that is not aligned, so that even sizes such as 512^3 converge; aligned transitions, and
+        so grids of sizes 2^k - 1, are unchanged bit for bit). GpuSolveError, with nothing changed, on a Z-slab grid."""
+        if mode not in _TRANSFERS:
+            raise ValueError(f"transfer must be one of {sorted(_TRANSFERS)}")
+        _check(driver().gs_grid_set_transfer(self.handle, _TRANSFERS[mode]))
+
+    @property
+    def transfer(self) -> str:
+        """The transfer mode in force (set_transfer or GS_TRANSFER): "reference" or "position"."""
+        m = driver().gs_grid_get_transfer(self.handle)
+        return next(k for k, v in _TRANSFERS.items() if v == m)
+
+    def level_aligned(self, level: int) -> bool:
+        """Whether the transition from `level` to `level + 1` is aligned (fine n = 2 coarse n + 1 on all three axes:
+        the reference's transfers are exact there and POSITION mode changes nothing)."""
+        r = driver().gs_grid_level_aligned(self.handle, level)
+        if r < 0:
+            raise IndexError(level)
+        return bool(r)
 
     def field(self, level: int, name: str) -> np.ndarray:
         """Copy of a padded field as a dense array indexed [x][y][z] (the reference's axis order)."""
@@ -294,6 +319,22 @@ def parse_omegas(text: str, pre: int, post: int) -> Tuple[Tuple[float, ...], Tup
     out = (C.c_double * max(1, pre + post))()
     _check(driver().gs_parse_omegas(text.encode(), int(pre), int(post), out))
     return tuple(out[:pre]), tuple(out[pre:pre + post])
+
+
+def transfer_axis(nf: int):
+    """The position-aware transfer tables of one axis for fine nf -> coarse nf // 2 (gs_transfer_axis; pure host
+    code, no device needed): dict of pj (int32, nf + 2), pt (nf + 2), rlo, rcnt (int32, nf // 2 + 2) and rw
+    ((nf // 2 + 2, 4)). ValueError for nf < 2."""
+    nf = int(nf)
+    nc = nf // 2
+    pj, pt = np.zeros(max(nf, 0) + 2, np.int32), np.zeros(max(nf, 0) + 2)
+    rlo, rcnt, rw = np.zeros(nc + 2, np.int32), np.zeros(nc + 2, np.int32), np.zeros((nc + 2, 4))
+    i32 = C.POINTER(C.c_int32)
+    rc = transfer().gs_transfer_axis(nf, nc, pj.ctypes.data_as(i32), pt.ctypes.data_as(_abi.dptr),
+                                     rlo.ctypes.data_as(i32), rcnt.ctypes.data_as(i32), rw.ctypes.data_as(_abi.dptr))
+    if rc:
+        raise ValueError(kernels().gs_strerror(rc).decode())
+    return {"pj": pj, "pt": pt, "rlo": rlo, "rcnt": rcnt, "rw": rw}
 
 
 def field_layout(nx: int, ny: int, nz: int):

@@ -11,6 +11,7 @@ PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))  # gpu-so
 LIB_DIR = os.path.join(PKG_ROOT, "lib")
 BIN_DIR = os.path.join(PKG_ROOT, "bin")
 KERNEL_LIB = os.path.join(LIB_DIR, "libgpusolve_hip.so")
+TRANSFER_LIB = os.path.join(LIB_DIR, "libgpusolve_transfer.so")  # position-aware transfers (include/gpusolve_transfer.h)
 DIAG_LIB = os.path.join(LIB_DIR, "libgpusolve_diag.so")  # tools/ and tests/ only (include/gpusolve_diag.h)
 DRIVER_LIB = os.path.join(LIB_DIR, "libgpusolve_driver.so")
 EXECUTABLE = os.path.join(BIN_DIR, "GpuSolve-hip")
@@ -19,6 +20,7 @@ GS_LINEAR, GS_NONLINEAR, GS_NEWTON = 0, 1, 2
 GS_NEWTON_B = 3  # NEWTON with the precomputed linearisation factor B (include/gpusolve_hip.h)
 GS_NEWTON_G = 4  # GS_NEWTON_B whose factor field holds gamma everywhere (the first Newton iteration)
 GS_EINVAL = 100001
+GS_TRANSFER_REFERENCE, GS_TRANSFER_POSITION = 0, 1  # gs_grid_set_transfer (include/gpusolve_driver.h)
 GS_MAX_WEIGHTS = 8  # per-sweep relaxation weights per smoothing leg (include/gpusolve_hip.h)
 
 dptr = C.POINTER(C.c_double)
@@ -41,6 +43,12 @@ class gs_coarse_level(C.Structure):
 class gs_params(C.Structure):
     _fields_ = [("maxiter", i64), ("tol", C.c_double), ("dims", i64 * 3), ("mode", C.c_int), ("pre", i64),
                 ("post", i64), ("omega", C.c_double), ("gamma", C.c_double), ("stencil", gs_stencil)]
+
+
+class gs_transfer_tables(C.Structure):
+    """include/gpusolve_transfer.h: nf / nc per axis (host metadata), then device pointers per axis."""
+    _fields_ = [("nf", i64 * 3), ("nc", i64 * 3), ("pj", C.c_void_p * 3), ("pt", C.c_void_p * 3),
+                ("rlo", C.c_void_p * 3), ("rcnt", C.c_void_p * 3), ("rw", C.c_void_p * 3)]
 
 
 # name -> (restype, argtypes); void* is used for device pointers and streams
@@ -149,6 +157,19 @@ KERNEL_API = {
     "gs_build_info": (C.c_char_p, []),
 }
 
+# libgpusolve_transfer.so (include/gpusolve_transfer.h): the position-aware grid transfers
+TRANSFER_API = {
+    "gs_transfer_axis": (C.c_int, [i64, i64, C.POINTER(C.c_int32), dptr, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                   dptr]),
+    "gs_restrict_pa": (C.c_int, [C.c_void_p, C.POINTER(gs_level), C.c_void_p, C.c_void_p, C.POINTER(gs_level),
+                                 C.POINTER(gs_transfer_tables), C.c_void_p]),
+    "gs_prolong_add_pa": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(gs_level), C.c_void_p, C.POINTER(gs_level),
+                                    C.POINTER(gs_transfer_tables), C.c_void_p]),
+    "gs_residual_restrict_pa": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int, C.c_double, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(gs_level),
+                                          C.POINTER(gs_transfer_tables), C.c_void_p]),
+}
+
 DRIVER_API = {
     "gs_parse_config": (C.c_int, [C.c_char_p, C.POINTER(gs_params)]),
     "gs_grid_create": (C.c_void_p, [C.POINTER(gs_params)]),
@@ -158,6 +179,9 @@ DRIVER_API = {
     "gs_grid_vcycle_level": (C.c_int, [C.c_void_p, C.c_int]),
     "gs_grid_fmg": (C.c_int, [C.c_void_p, C.c_int, dptr]),
     "gs_grid_fmg_start_level": (C.c_int, [C.c_void_p]),
+    "gs_grid_set_transfer": (C.c_int, [C.c_void_p, C.c_int]),
+    "gs_grid_get_transfer": (C.c_int, [C.c_void_p]),
+    "gs_grid_level_aligned": (C.c_int, [C.c_void_p, C.c_int]),
     "gs_grid_set_weights": (C.c_int, [C.c_void_p, dptr, C.c_int, dptr, C.c_int]),
     "gs_grid_get_weights": (C.c_int, [C.c_void_p, dptr, dptr]),
     "gs_chebyshev_weights": (C.c_int, [C.c_int, C.c_double, C.c_double, dptr]),
@@ -257,6 +281,12 @@ def kernels():
     return _load(KERNEL_LIB, KERNEL_API)
 
 
+def transfer():
+    """The position-aware transfer library (libgpusolve_transfer.so)."""
+    kernels()
+    return _load(TRANSFER_LIB, TRANSFER_API)
+
+
 def diag():
     """The diagnostics library (libgpusolve_diag.so): measurement and tuning code, never the product path."""
     kernels()
@@ -264,6 +294,6 @@ def diag():
 
 
 def driver():
-    """The host driver library (libgpusolve_driver.so); loads the kernel library first."""
-    kernels()
+    """The host driver library (libgpusolve_driver.so); loads the kernel libraries first."""
+    transfer()
     return _load(DRIVER_LIB, DRIVER_API)

@@ -87,6 +87,23 @@ int gs_chebyshev_weights(int nu, double lo, double hi, double* out);
  * pre + post weights into out (which may be NULL: validation only). 1 (and gs_last_error()) on a malformed value, a
  * count mismatch, a non-finite weight or more than GS_MAX_WEIGHTS weights per leg. */
 int gs_parse_omegas(const char* text, int pre, int post, double* out);
+/* Grid transfers (added). GS_TRANSFER_REFERENCE, the default: the reference's index-aligned restrict /
+ * interpolate on every transition — exact only where fine n = 2 coarse n + 1, so V-cycles on even sizes (every power
+ * of two) do not converge. GS_TRANSFER_POSITION: every transition that is not aligned takes the position-aware
+ * operators of gpusolve_transfer.h (gs_residual_restrict_pa, gs_restrict_pa, gs_prolong_add_pa between the level's
+ * ordinary sweeps; the tiled steps, the fused prolongation pairs and the one-launch coarse cycle are not taken there),
+ * aligned transitions are unchanged launch for launch: on sizes 2^k - 1 the two modes give the same bits. Applies to
+ * gs_grid_solve in all three modes, gs_grid_vcycle and gs_grid_vcycle_level; gs_grid_fmg keeps its alignment
+ * requirement in either mode. The tables of the non-aligned transitions are built and uploaded when POSITION is first
+ * switched on. Fails (return 1, gs_last_error(), nothing changed) for any other mode value and for POSITION on a
+ * Z-slab / RCCL grid. GS_TRANSFER=position|reference in the environment when the grid is created sets the mode; any
+ * other value fails the creation. */
+enum { GS_TRANSFER_REFERENCE = 0, GS_TRANSFER_POSITION = 1 };
+int gs_grid_set_transfer(void* grid, int mode);
+int gs_grid_get_transfer(void* grid);
+/* 1 if the transition from `level` to `level + 1` is aligned (fine n = 2 coarse n + 1 on all three axes), 0 if not,
+ * -1 if there is no such transition. */
+int gs_grid_level_aligned(void* grid, int level);
 int gs_grid_jacobi(void* grid, int level, int sweeps);
 int gs_grid_residual_norm(void* grid, int level, double* norm);
 int gs_grid_num_levels(void* grid);
