@@ -44,7 +44,22 @@ void gs_grid_destroy(void* grid);
 
 /* Runs the solve selected by the mode. print: 0 silent, 1 reference stdout lines.
  * Writes up to cap residual values (initial, then one per V-cycle / Newton iteration) into hist
- * and their total count into *count. */
+ * and their total count into *count.
+ *
+ * What a grid holds between calls (tests/session_ref.py is this rule as a CPU model, tests/test_gpu_sessions.py holds
+ * the driver to it). Level 0's v (NEWTON: newtonV) and f are always the reference's. On the levels below:
+ *   - gs_grid_vcycle, gs_grid_fmg and a solve that ran all its cycles (or stopped on its last one) leave every level's
+ *     v and f as that last V-cycle left them: f the restricted residual (FAS: + A(restV)), v the post-smoothed iterate.
+ *     NONLINEAR: v is the FAS iterate itself; the reference overwrites it with the correction v - restV
+ *     (CpuSolver.cpp:121-124), which the driver only forms on the fly.
+ *   - a LINEAR / NONLINEAR solve that stopped on tol BEFORE its last cycle leaves v and f of the levels >= 1
+ *     unspecified: with the cycles pipelined, the next cycle's down-leg has run on them already (level 0 is restored
+ *     exactly: the adoption of the speculative sweeps is undone); with GS_NO_PIPELINE or GS_NO_SPECULATION it has not.
+ *     Upload a level's v and f (gs_grid_upload) or run a V-cycle from above it before reading it.
+ *   - gs_grid_vcycle_level(l) reads level l's v and f and defines the levels below l; the levels above are not touched.
+ *   - NEWTON: after a solve only level 0's newtonV is defined; v and f of every level are the inner solves' work fields.
+ *   - every field is handed back stored: a zero iterate the driver keeps as a flag is never visible to gs_grid_download,
+ *     and gs_grid_upload of a level's v is what the next operation on that level reads. */
 int gs_grid_solve(void* grid, int print, double* hist, int cap, int* count);
 
 int gs_grid_vcycle(void* grid, double* residual);

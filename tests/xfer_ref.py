@@ -103,9 +103,9 @@ class Cycle(weights_ref.Cycle):
     linearisation point newtonV)."""
 
     def __init__(self, dims, mode=O.LINEAR, pre=(0.8, 0.8), post=(0.8, 0.8), gamma=1.0, f0=None, v0=None,
-                 transfer="position", w=None):
+                 transfer="position", w=None, stencil=None):
         inner = O.LINEAR if mode == O.NEWTON else mode
-        super().__init__(dims, inner, pre, post, gamma, f0=f0, v0=v0)
+        super().__init__(dims, inner, pre, post, gamma, f0=f0, v0=v0, stencil=stencil)
         self.mode, self.transfer, self.w = mode, transfer, w
         if f0 is None and mode == O.NEWTON:
             self.f[0] = O.rhs(*self.ld[0], mode, gamma)
@@ -127,10 +127,10 @@ class Cycle(weights_ref.Cycle):
     def _smooth(self, l, weights):
         for om in weights:
             self.v[l] = O.jacobi(self.v[l], self.f[l], self.h[l], mode=self.mode, omega=float(om), gamma=self.gamma,
-                                 sweeps=1, w=self._w(l))
+                                 sweeps=1, w=self._w(l), stencil=self.stencil)
 
     def residual(self, l=0):
-        return O.residual(self.v[l], self.f[l], self.h[l], self.mode, self.gamma, w=self._w(l))
+        return O.residual(self.v[l], self.f[l], self.h[l], self.mode, self.gamma, w=self._w(l), stencil=self.stencil)
 
     def vcycle_from(self, root=0):
         nl = len(self.ld)
@@ -144,7 +144,7 @@ class Cycle(weights_ref.Cycle):
             else:
                 rest[l + 1] = self.R(l, self.v[l])
                 self.v[l + 1] = rest[l + 1].copy()
-                self.f[l + 1] = self.f[l + 1] + O.apply_op(rest[l + 1], self.h[l + 1], self.gamma)
+                self.f[l + 1] = self.f[l + 1] + O.apply_op(rest[l + 1], self.h[l + 1], self.gamma, self.stencil)
         self._smooth(nl - 1, self.pre + self.post)
         for l in range(nl - 1, root, -1):
             c = self.v[l] - rest[l] if self.mode == O.NONLINEAR else self.v[l]
@@ -152,17 +152,19 @@ class Cycle(weights_ref.Cycle):
             self._smooth(l - 1, self.post)
 
 
-def newton_solve(dims, iters, transfer="position", pre=(0.8, 0.8), post=(0.8, 0.8), gamma=1.0):
+def newton_solve(dims, iters, transfer="position", pre=(0.8, 0.8), post=(0.8, 0.8), gamma=1.0, stencil=None, w0=None):
     """NewtonSolver::solve as oracle/gs_oracle.cpp restates it (inner solve: at most 10 V-cycles, tol 0.1), with the
-    transfers chosen per transition: (history, level-0 newtonV)."""
+    transfers chosen per transition: (history, level-0 newtonV). w0: level 0's initial newtonV (default zero)."""
     ld = level_dims(dims)
     h0 = 1.0 / (ld[0][1] + 1)
     F = O.rhs(*ld[0], O.NEWTON, gamma)
     w = [O.zeros(*d) for d in ld]
-    f0, r0 = O.newton_F(w[0], F, h0, gamma)
+    if w0 is not None:
+        w[0] = np.ascontiguousarray(w0, dtype=np.float64).copy()
+    f0, r0 = O.newton_F(w[0], F, h0, gamma, stencil)
     hist = [r0]
     for _ in range(iters):
-        c = Cycle(dims, O.NEWTON, pre, post, gamma, f0=f0, transfer=transfer, w=w)
+        c = Cycle(dims, O.NEWTON, pre, post, gamma, f0=f0, transfer=transfer, w=w, stencil=stencil)
         for l in range(1, len(ld) - 1):  # the coarsest level keeps its newtonV
             w[l] = c.R(l - 1, w[l - 1])
         start = c.residual(0)[1]
@@ -170,6 +172,6 @@ def newton_solve(dims, iters, transfer="position", pre=(0.8, 0.8), post=(0.8, 0.
             if c.vcycle() <= start / (1.0 / 0.1):
                 break
         w[0] = w[0] + c.v[0]
-        f0, res = O.newton_F(w[0], F, h0, gamma)
+        f0, res = O.newton_F(w[0], F, h0, gamma, stencil)
         hist.append(res)
     return hist, w[0]
