@@ -195,6 +195,13 @@ int gs_grid_set_transfer(void* grid, int mode)
 
 int gs_grid_get_transfer(void* grid) { return G(grid).transferMode; }
 
+int gs_grid_set_fmg_prolong(void* grid, int mode)
+{
+    return guarded([&] { G(grid).setFmgProlong(mode); });
+}
+
+int gs_grid_get_fmg_prolong(void* grid) { return G(grid).fmgProlongMode; }
+
 int gs_grid_level_aligned(void* grid, int level)
 {
     if (level < 0 || level + 1 >= (int)G(grid).numLevels()) return -1;

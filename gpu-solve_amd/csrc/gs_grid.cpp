@@ -214,6 +214,14 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
             throw Error("GS_TRANSFER=" + t + ": the value must be position or reference");
     }
     if (transferEnv == 1 && (nranks() > 1 || traceLog)) throw Error(kTransferSingleGpu); // before any work or collective
+    // GS_FMG_PROLONG=position|aligned: full multigrid's prolongation (setFmgProlong, once the levels exist)
+    int fmgProlongEnv = 0;
+    if (const char* e = std::getenv("GS_FMG_PROLONG")) {
+        const std::string t = e;
+        if (t == "position") fmgProlongEnv = 1;
+        else if (t != "aligned")
+            throw Error("GS_FMG_PROLONG=" + t + ": the value must be position or aligned");
+    }
     std::vector<int64_t> nzs, pts;
     for (int l = 0; l < nlev; l++) {
         LevelData& L = levels_[l];
@@ -287,6 +295,7 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
     }
     coarseFromRef_ = coarseFrom;
     xferT_.assign(levels_.size(), gs_transfer_tables{});
+    fmgT_.assign(levels_.size(), gs_fmg_tables{});
     if (mode == NEWTON) newtonF = DeviceField(levels_[0].geom.nx, levels_[0].geom.ny, levels_[0].geom.nz, s, dry);
     newtonVZero_ = mode == NEWTON; // (every field is created zero-filled)
     {
@@ -299,6 +308,7 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
         partials_ = dryParts_.data();
         rec("rhs", {{"L", 0}}, "f");
         halo(levels_[0], levels_[0].f, s);
+        if (fmgProlongEnv) setFmgProlong(fmgProlongEnv);
         return;
     }
     // the overlapped sweep splits a level into 3 launches, each with its own partials region
@@ -350,6 +360,7 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
     }
     check((int)hipStreamSynchronize(s), "hipStreamSynchronize");
     if (transferEnv) setTransfer(transferEnv);
+    if (fmgProlongEnv) setFmgProlong(fmgProlongEnv);
 }
 
 bool HipGridData::levelAligned(std::size_t l) const
@@ -416,6 +427,49 @@ void HipGridData::setTransfer(int m)
         std::size_t c = nl - 1;
         while (c > coarseFromRef_ && levelAligned(c - 1)) c--;
         coarseFrom = c;
+    }
+}
+
+void HipGridData::setFmgProlong(int m)
+{
+    if (m != 0 && m != 1)
+        throw Error("fmg prolong: the mode must be GS_FMG_PROLONG_ALIGNED (0) or GS_FMG_PROLONG_POSITION (1)");
+    if (m == 1) buildFmgTables();
+    fmgProlongMode = m;
+}
+
+void HipGridData::buildFmgTables()
+{
+    if (mode == NEWTON || nranks() > 1 || trace) return; // FMG is refused there: no table is ever read
+    for (std::size_t l = 0; l + 1 < levels_.size(); l++) {
+        if (levelAligned(l) || fmgT_[l].cj[0]) continue;
+        // one allocation per transition: per axis cw (4 (nf + 2) doubles), then per axis cj (nf + 2)
+        gs_fmg_tables T{};
+        std::vector<std::vector<int32_t>> cj(3);
+        std::vector<std::vector<double>> cw(3);
+        std::size_t bytes = 0;
+        for (int a = 0; a < 3; a++) {
+            const int64_t nf = (int64_t)levels_[l].levelDim[a], nc = (int64_t)levels_[l + 1].levelDim[a];
+            T.nf[a] = nf;
+            T.nc[a] = nc;
+            cj[a].resize(nf + 2);
+            cw[a].resize(4 * (nf + 2));
+            check(gs_fmg_axis(nf, nc, cj[a].data(), cw[a].data()), "gs_fmg_axis");
+            bytes += sizeof(double) * cw[a].size() + sizeof(int32_t) * cj[a].size();
+        }
+        char* base = nullptr;
+        check((int)hipMalloc((void**)&base, bytes), "hipMalloc(fmg tables)");
+        xferMem_.push_back(base);
+        std::size_t off = 0;
+        auto put = [&](const void* src, std::size_t n) {
+            check((int)hipMemcpy(base + off, src, n, hipMemcpyHostToDevice), "hipMemcpy(fmg tables)");
+            const void* p = base + off;
+            off += n;
+            return p;
+        };
+        for (int a = 0; a < 3; a++) T.cw[a] = (const double*)put(cw[a].data(), sizeof(double) * cw[a].size());
+        for (int a = 0; a < 3; a++) T.cj[a] = (const int32_t*)put(cj[a].data(), sizeof(int32_t) * cj[a].size());
+        fmgT_[l] = T;
     }
 }
 
@@ -1410,6 +1464,7 @@ void HipSolver::vcycleFrom(HipGridData& grid, std::size_t level)
 std::size_t HipSolver::fmgStartLevel(const HipGridData& grid)
 {
     if (grid.mode == GridParams::NEWTON || grid.nranks() > 1 || grid.trace) return 0;
+    if (grid.fmgProlongMode == 1) return grid.numLevels() - 1; // every transition can be prolonged
     std::size_t s = 0;
     while (s + 1 < grid.numLevels() && gs_fmg_prolong_supported(&grid.getLevel(s + 1).geom, &grid.getLevel(s).geom)) s++;
     return s;
@@ -1422,6 +1477,15 @@ void HipSolver::fmgCheck(const HipGridData& grid, int cyclesPerLevel)
     if (grid.nranks() > 1 || grid.trace)
         throw Error("FMG: single-GPU grids only (not a Z-slab / RCCL or schedule-trace grid)");
     if (cyclesPerLevel < 1) throw Error("FMG: cycles per level must be at least 1");
+    if (grid.fmgProlongMode == 1 && grid.transferMode == 0)
+        for (std::size_t l = 0; l + 1 < grid.numLevels(); l++)
+            if (!grid.levelAligned(l)) {
+                const auto& d = grid.getLevel(0).levelDim;
+                throw Error("FMG: the position-aware prolongation (GS_FMG_PROLONG=position) on " + std::to_string(d[0]) +
+                            " x " + std::to_string(d[1]) + " x " + std::to_string(d[2]) +
+                            ", whose coarse grids do not all align, needs the position-aware transfers for its V-cycles: "
+                            "gs_grid_set_transfer(GS_TRANSFER_POSITION) / GS_TRANSFER=position");
+            }
     if (fmgStartLevel(grid) == 0) {
         const auto& d = grid.getLevel(0).levelDim;
         throw Error("FMG: the coarse grids of " + std::to_string(d[0]) + " x " + std::to_string(d[1]) + " x " +
@@ -1436,7 +1500,9 @@ void HipSolver::fmgRun(HipGridData& grid, int cyclesPerLevel)
     fmgCheck(grid, cyclesPerLevel);
     const hipStream_t s = grid.stream();
     const std::size_t start = fmgStartLevel(grid);
-    // f^(l+1) = R f^l from level 0's f as it stands (a V-cycle rooted at level l only writes f below l)
+    if (grid.fmgProlongMode == 1) grid.buildFmgTables();
+    // f^(l+1) = R f^l from level 0's f as it stands (a V-cycle rooted at level l only writes f below l); restrict()
+    // takes gs_restrict_pa on the transitions the grid's POSITION transfers cover
     for (std::size_t l = 0; l < start; l++) restrict(grid, grid.getLevel(l).f, l, grid.getLevel(l + 1).f);
     for (std::size_t l = start + 1; l-- > 0;) {
         auto& L = grid.getLevel(l);
@@ -1451,7 +1517,11 @@ void HipSolver::fmgRun(HipGridData& grid, int cyclesPerLevel)
         } else {
             auto& C = grid.getLevel(l + 1);
             materialize(grid, l + 1);
-            check(gs_fmg_prolong(C.v.data(), &C.geom, L.v.data(), &L.geom, s), "gs_fmg_prolong");
+            if (grid.fmgProlongMode == 1 && !grid.levelAligned(l))
+                check(gs_fmg_prolong_pa(C.v.data(), &C.geom, L.v.data(), &L.geom, grid.fmgTables(l), s),
+                      "gs_fmg_prolong_pa");
+            else
+                check(gs_fmg_prolong(C.v.data(), &C.geom, L.v.data(), &L.geom, s), "gs_fmg_prolong");
             L.vZero = false;
         }
         for (int c = 0; c < cyclesPerLevel; c++) vcycleFrom(grid, l);

@@ -201,6 +201,17 @@ public:
     bool levelAligned(std::size_t l) const; // the transition l -> l + 1 (l + 1 < numLevels())
     bool pa(std::size_t l) const { return transferMode == 1 && !levelAligned(l); }
     const gs_transfer_tables* xfer(std::size_t l) const { return &xferT_[l]; }
+    // Full multigrid's prolongation (gs_grid_set_fmg_prolong, GS_FMG_PROLONG). 0, the default (ALIGNED): gs_fmg_prolong
+    // on aligned transitions only, so FMG starts at the deepest level above which every transition is aligned and is
+    // refused where that is level 0. 1 (POSITION): FMG starts at the coarsest level; an aligned transition keeps
+    // gs_fmg_prolong, every other one takes gs_fmg_prolong_pa (and needs the POSITION transfers for its V-cycles:
+    // fmgCheck). NEWTON, Z-slab and trace grids keep the mode and stay refused by FMG.
+    int fmgProlongMode = 0;
+    // builds and uploads the tables of every non-aligned transition the first time POSITION is switched on (on a grid
+    // FMG can run on). Throws, leaving the grid as it was.
+    void setFmgProlong(int mode);
+    void buildFmgTables(); // (no-op once built, or where FMG is refused anyway)
+    const gs_fmg_tables* fmgTables(std::size_t l) const { return &fmgT_[l]; }
     // where the position-aware path is taken, f^2h = R(f^h - A v^h) in one pass (gs_residual_restrict_pa) rather
     // than gs_residual with a stored r followed by gs_restrict_pa (DESIGN.md §4.9 has the A/B)
     static constexpr bool paFusedRR = true;
@@ -279,7 +290,8 @@ private:
     long traceNorms_ = 0;
     std::size_t coarseFromRef_ = 0;          // coarseFrom of the REFERENCE transfers (GS_COARSE_POINTS' rule)
     std::vector<gs_transfer_tables> xferT_;  // per transition l -> l + 1; null pointers where aligned or not built
-    std::vector<void*> xferMem_;             // the device allocations behind them
+    std::vector<gs_fmg_tables> fmgT_;        // the same for gs_fmg_prolong_pa
+    std::vector<void*> xferMem_;             // the device allocations behind both
     bool haloPending_ = false; // an exchange issued by haloIssue, not settled
     friend class NewtonSolver;
     bool newtonR1_ = false;    // level 1's newtonVNext holds R(level 0's newtonV) (gs_newton_F_update_restrict)
@@ -323,9 +335,12 @@ public:
     // restriction of level 0's f as it stands; the start level s (fmgStartLevel) is iterated from zero and each
     // finer level from the tricubic prolongation (gs_fmg_prolong) of the level below, cyclesPerLevel V-cycles
     // each. Overwrites v on every level; returns the level-0 residual norm. LINEAR and NONLINEAR (FAS) grids on
-    // one GPU whose coarse grids align (sizes 2^k - 1); otherwise throws before any work (fmgCheck).
+    // one GPU whose coarse grids align (sizes 2^k - 1); otherwise throws before any work (fmgCheck). With
+    // grid.fmgProlongMode POSITION: every size, from the coarsest level, non-aligned transitions prolonged by
+    // gs_fmg_prolong_pa and restricted by gs_restrict_pa (the grid's transfers must be POSITION where one exists).
     static double fmg(HipGridData& grid, int cyclesPerLevel);
-    // the deepest level such that every transition above it is gs_fmg_prolong_supported; 0: FMG not applicable
+    // the deepest level such that every transition above it is gs_fmg_prolong_supported (POSITION prolongation: the
+    // coarsest level); 0: FMG not applicable
     static std::size_t fmgStartLevel(const HipGridData& grid);
     static void fmgCheck(const HipGridData& grid, int cyclesPerLevel); // throws what fmg would
     static void fmgRun(HipGridData& grid, int cyclesPerLevel);         // fmg without the closing norm

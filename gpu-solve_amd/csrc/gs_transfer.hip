@@ -33,6 +33,18 @@ PaTables device_tables(const gs_transfer_tables* T)
     return d;
 }
 
+bool bad_fmg_transfer(const gs_level* fl, const gs_level* cl, const gs_fmg_tables* T)
+{
+    if (bad_level(fl) || bad_level(cl) || !T || fl->z0 != 0 || cl->z0 != 0) return true;
+    const int64_t nf[3] = {fl->nx, fl->ny, fl->nz}, nc[3] = {cl->nx, cl->ny, cl->nz};
+    for (int a = 0; a < 3; a++) {
+        if (nf[a] < 2 || nc[a] != nf[a] / 2 || T->nf[a] != nf[a] || T->nc[a] != nc[a]) return true;
+        if (!T->cj[a] || !T->cw[a]) return true;
+    }
+    if (cl->ldy > INT32_MAX / 16) return true; // (the kernel's 32-bit offsets inside a staged tile)
+    return false;
+}
+
 } // namespace
 
 extern "C" {
@@ -67,6 +79,66 @@ int gs_transfer_axis(int64_t nf, int64_t nc, int32_t* pj, double* pt, int32_t* r
         if (rem > 0 && !feed(j + 1, i, s * pt[i])) return GS_EINVAL;
     }
     return 0;
+}
+
+int gs_fmg_axis(int64_t nf, int64_t nc, int32_t* cj, double* cw)
+{
+    if (nf < 2 || nf > INT32_MAX / 2 || nc != nf / 2 || !cj || !cw) return GS_EINVAL;
+    const int64_t D = nf + 1, P = nc + 2;
+    cj[0] = cj[nf + 1] = 0;
+    for (int k = 0; k < 4; k++) cw[k] = cw[4 * (nf + 1) + k] = 0.0;
+    for (int64_t i = 1; i <= nf; i++) {
+        const int64_t q = i * (nc + 1), pj = q / D, rem = q % D;
+        const int64_t c = P >= 4 ? std::min(std::max(pj - 1, (int64_t)0), P - 4) : 0;
+        const double t = (double)(pj - c) + (double)rem / (double)D;
+        double* w = cw + 4 * i;
+        cj[i] = (int32_t)c;
+        if (P >= 4) {
+            w[0] = -(((t - 1) * (t - 2)) * (t - 3)) / 6;
+            w[1] = ((t * (t - 2)) * (t - 3)) / 2;
+            w[2] = -((t * (t - 1)) * (t - 3)) / 2;
+            w[3] = ((t * (t - 1)) * (t - 2)) / 6;
+        } else {
+            w[0] = ((t - 1) * (t - 2)) / 2;
+            w[1] = -(t * (t - 2));
+            w[2] = (t * (t - 1)) / 2;
+            w[3] = 0.0;
+        }
+    }
+    return 0;
+}
+
+int gs_fmg_prolong_pa(const double* coarse, const gs_level* cl, double* fine, const gs_level* fl,
+                      const gs_fmg_tables* T, hipStream_t st)
+{
+    if (!coarse || !fine || bad_fmg_transfer(fl, cl, T)) return GS_EINVAL;
+    // non-temporal fine stores for a stream larger than the Infinity Cache, as gs_fmg_prolong (GS_FMG_NT: A/B)
+    const bool nt = kKnobs.fmgNt < 0 ? fl->nx * fl->ny * fl->nz >= ((int64_t)1 << 25) : kKnobs.fmgNt != 0;
+    // fine planes per block: 16 on levels that do not fill the chip, else the even chunk of 16..128 that makes the
+    // grid whole rounds of resident blocks (fit_chunk; a chunk stages about three coarse planes, six fine ones, more
+    // than it covers)
+    const int64_t tiles = ((fl->nx + 2 * FQ_TX - 1) / (2 * FQ_TX)) * ((fl->ny + 2 * FQ_TY - 1) / (2 * FQ_TY));
+    const void* fn = nt ? (const void*)k_fmg_prolong_pa<true> : (const void*)k_fmg_prolong_pa<false>;
+    int zc = fit_chunk(tiles, fl->nz, resident_blocks(fn, FQ_T), 16, 128, true, 6.0);
+    if (zc < 16) zc = tiles >= 256 && fl->nz >= 256 ? 64 : 16; // (GS_FIT_ROUNDS=0)
+    const dim3 g((unsigned)((fl->nx + 2 * FQ_TX - 1) / (2 * FQ_TX)), (unsigned)((fl->ny + 2 * FQ_TY - 1) / (2 * FQ_TY)),
+                 (unsigned)((fl->nz + zc - 1) / zc)),
+        b(FQ_TX, FQ_TY);
+    if (g.y > 65535u || g.z > 65535u) return GS_EINVAL;
+    FqTables d;
+    for (int a = 0; a < 3; a++) {
+        d.cj[a] = T->cj[a];
+        d.cw[a] = T->cw[a];
+    }
+    // the fine pair (x odd, x + 1) as one 16-byte store where the layout aligns it (gs_field_layout does)
+    const int al = ((reinterpret_cast<uintptr_t>(fine + 1) & 15) == 0 && fl->ldy % 2 == 0 && fl->ldz % 2 == 0) ? 1 : 0;
+    if (nt)
+        hipLaunchKernelGGL(k_fmg_prolong_pa<true>, g, b, 0, st, d, coarse, fine, (int)cl->nx, (int)cl->ny, (int)cl->nz,
+                           (int)fl->nx, (int)fl->ny, (int)fl->nz, cl->ldy, cl->ldz, fl->ldy, fl->ldz, zc, al);
+    else
+        hipLaunchKernelGGL(k_fmg_prolong_pa<false>, g, b, 0, st, d, coarse, fine, (int)cl->nx, (int)cl->ny, (int)cl->nz,
+                           (int)fl->nx, (int)fl->ny, (int)fl->nz, cl->ldy, cl->ldz, fl->ldy, fl->ldz, zc, al);
+    return launch_status();
 }
 
 int gs_restrict_pa(const double* fine, const gs_level* fl, double* coarse_a, double* coarse_b, const gs_level* cl,

@@ -311,4 +311,192 @@ __global__ __launch_bounds__(PA_T) void k_resrestrict_pa(Coef k, PaStencil so, P
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Full multigrid's prolongation by position (gs_fmg_prolong_pa): gs_device.hpp's k_fmg_prolong with the window start
+// cj and the four Lagrange weights of every fine index read from tables instead of following from 2i / 2i + 1.
+// One block: a fine tile of 2 FQ_TX x-points (a wave: the lane's points x, x + 1, x odd, as one 16-byte store) by
+// 2 FQ_TY rows (two per wave), marching a chunk of fine planes. Per coarse plane the block stages the columns
+// cj_x[first] .. cj_x[last] + K - 1 and rows cj_y[first] .. cj_y[last] + K - 1 of its tile in LDS (three buffers, one
+// barrier per plane; plane p + 1, loaded a step earlier, is written at the top of step p, then plane p + 2's loads
+// are issued into the same registers); each thread forms the x- and then y-interpolated values of its 2 x 2 fine
+// columns on that plane; the z pass runs on a register window of the last four such planes. cj_z is non-decreasing in
+// the fine plane and moves by 0 or 1, so after coarse plane p the fine planes with cj_z + K - 1 = p are complete, in
+// order.
+//  - 128 consecutive fine indices span at most 64 + K coarse ones, 8 at most 4 + K (pj advances by (m + 1) / (n + 1)
+//    per index: at most 130 / 258 where a tile is full in x, at most 5 / 9 where it is full in y): FQ_LW, FQ_LR.
+//  - A lane's 2 x 4 x-weights and the wave's 2 x 4 y-weights are loop invariants; the z-weights are wave-uniform,
+//    read when the plane before theirs has been emitted (the window start one plane further ahead).
+//  - K = 3 (one coarse point on the axis): the fourth operand is neither used nor, in global memory, read.
+//  - Every table value is clamped to the staged tile and the padded coarse array, so tables that do not belong to
+//    the levels cannot take an access out of either field.
+constexpr int FQ_TX = 64, FQ_TY = 4, FQ_T = FQ_TX * FQ_TY;
+constexpr int FQ_LW = FQ_TX + 4, FQ_LR = 2 * FQ_TY; // staged columns, rows
+constexpr int FQ_NE = (FQ_LW * FQ_LR + FQ_T - 1) / FQ_T; // staged elements per thread and plane
+
+struct FqTables {
+    const int32_t* cj[3];
+    const double* cw[3];
+};
+
+__device__ __forceinline__ double fq_sum(bool k3, const double (&w)[4], double c0, double c1, double c2, double c3)
+{
+    const double s = (w[0] * c0 + w[1] * c1) + w[2] * c2;
+    return k3 ? s : s + w[3] * c3;
+}
+
+template <bool NT>
+__global__ __launch_bounds__(FQ_T, 5) void k_fmg_prolong_pa(FqTables T, const double* __restrict__ c,
+                                                         double* __restrict__ f, int cnx, int cny, int cnz, int fnx,
+                                                         int fny, int fnz, int64_t cldy, int64_t cldz, int64_t fldy,
+                                                         int64_t fldz, int zc, int al)
+{
+    __shared__ double pl[3][FQ_LR * FQ_LW];
+    // (the wave's rows in SGPRs: their windows and weights are then scalar)
+    const int lane = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(threadIdx.y), tid = wv * FQ_TX + lane;
+    const bool k3x = cnx < 2, k3y = cny < 2, k3z = cnz < 2;
+    const int x0 = 1 + blockIdx.x * 2 * FQ_TX, y0 = 1 + blockIdx.y * 2 * FQ_TY, zb = 1 + blockIdx.z * zc;
+    const int xe = min(x0 + 2 * FQ_TX - 1, fnx), ye = min(y0 + 2 * FQ_TY - 1, fny), ze = min(zb + zc - 1, fnz);
+    // staged columns / rows / planes: what the tile's windows cover, inside the padded coarse array
+    const int clo = pa_clamp(T.cj[0][x0], 0, cnx + 1);
+    const int ncol = pa_clamp(T.cj[0][xe] + (k3x ? 3 : 4) - clo, 1, min(FQ_LW, cnx + 2 - clo));
+    const int rlo = pa_clamp(T.cj[1][y0], 0, cny + 1);
+    const int nrow = pa_clamp(T.cj[1][ye] + (k3y ? 3 : 4) - rlo, 1, min(FQ_LR, cny + 2 - rlo));
+    const int pstart = pa_clamp(T.cj[2][zb], 0, cnz + 1);
+    const int pend = pa_clamp(T.cj[2][ze] + (k3z ? 2 : 3), pstart, cnz + 1);
+    // the lane's two x-points and the wave's two rows: window positions in the staged plane, weights
+    const int x = x0 + 2 * lane, ya = y0 + 2 * wv;
+    const bool okx = x <= fnx, x2 = x + 1 <= fnx, oka = ya <= fny, okb = ya + 1 <= fny;
+    const int xa = min(x, fnx), xb = min(x + 1, fnx), yA = min(ya, fny), yB = min(ya + 1, fny);
+    const int lca = pa_clamp(T.cj[0][xa] - clo, 0, FQ_LW - 4), lcb = pa_clamp(T.cj[0][xb] - clo, 0, FQ_LW - 4);
+    const int lra = pa_clamp(T.cj[1][yA] - rlo, 0, FQ_LR - 4);
+    const bool dy = T.cj[1][yB] - rlo > lra; // row b's window starts one staged row later
+    double wxa[4], wxb[4], wya[4], wyb[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        wxa[k] = T.cw[0][4 * xa + k];
+        wxb[k] = T.cw[0][4 * xb + k];
+        wya[k] = T.cw[1][4 * yA + k];
+        wyb[k] = T.cw[1][4 * yB + k];
+    }
+    // the staged elements this thread loads per plane (offsets from cb: the launcher keeps FQ_LR * cldy inside an int)
+    const int n = nrow * ncol;
+    const double* const cb = c + clo + (int64_t)rlo * cldy;
+    int goff[FQ_NE], loff[FQ_NE];
+    bool gok[FQ_NE];
+#pragma unroll
+    for (int m = 0; m < FQ_NE; m++) {
+        const int e = tid + m * FQ_T;
+        gok[m] = e < n;
+        const int r = gok[m] ? e / ncol : 0, col = gok[m] ? e - r * ncol : 0;
+        goff[m] = col + r * (int)cldy;
+        loff[m] = r * FQ_LW + col;
+    }
+    // plane pstart goes to LDS now; g: the thread's elements of the plane after the one being computed, loaded a step
+    // earlier and written to the third buffer at the top of the step
+    double g[FQ_NE];
+#pragma unroll
+    for (int m = 0; m < FQ_NE; m++) g[m] = gok[m] ? cb[goff[m] + (int64_t)pstart * cldz] : 0.0;
+#pragma unroll
+    for (int m = 0; m < FQ_NE; m++)
+        if (gok[m]) pl[0][loff[m]] = g[m];
+#pragma unroll
+    for (int m = 0; m < FQ_NE; m++) g[m] = gok[m] && pstart < pend ? cb[goff[m] + (int64_t)(pstart + 1) * cldz] : 0.0;
+    __syncthreads();
+
+    // the z tables of the fine plane to emit next: window start (and that of the plane after it), weights
+    auto zidx = [&](int z) { return min(z, fnz + 1); };
+    int z = zb, cjc = T.cj[2][zidx(zb)], cjn = T.cj[2][zidx(zb + 1)];
+    double wz[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) wz[k] = T.cw[2][4 * zidx(zb) + k];
+
+    // [plane of the window][row a: x, x + 1; row b: x, x + 1]
+    double W[4][4];
+#pragma unroll
+    for (int m = 0; m < 4; m++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) W[m][q] = 0.0;
+    double* const frow = f + x + (int64_t)ya * fldy;
+    auto store = [&](double* p, double a, double b) {
+        if (x2) {
+            if (al) st2s<NT>(p, a, b);
+            else {
+                p[0] = a;
+                p[1] = b;
+            }
+        } else {
+            p[0] = a;
+        }
+    };
+
+    int cur = 0;
+    for (int p = pstart; p <= pend; p++) {
+        // plane p + 1 into the buffer last read two steps ago; plane p + 2's loads are in flight during this step
+        const int nxt = cur == 2 ? 0 : cur + 1;
+        if (p < pend) {
+#pragma unroll
+            for (int m = 0; m < FQ_NE; m++)
+                if (gok[m]) pl[nxt][loff[m]] = g[m];
+        }
+#pragma unroll
+        for (int m = 0; m < FQ_NE; m++) g[m] = gok[m] && p + 2 <= pend ? cb[goff[m] + (int64_t)(p + 2) * cldz] : 0.0;
+#pragma unroll
+        for (int m = 0; m < 3; m++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) W[m][q] = W[m + 1][q];
+        // x pass on the five staged rows the two windows cover (the fifth only where they differ); every row's values go
+        // straight into the y sums, which take their terms in window order: row a's term m, row b's term m - dy
+#pragma unroll
+        for (int m = 0; m < 5; m++) {
+            if (m == 4 && (!dy || k3y)) continue;
+            const double* row = pl[cur] + min(lra + m, FQ_LR - 1) * FQ_LW;
+            const double va = fq_sum(k3x, wxa, row[lca], row[lca + 1], row[lca + 2], row[lca + 3]);
+            const double vb = fq_sum(k3x, wxb, row[lcb], row[lcb + 1], row[lcb + 2], row[lcb + 3]);
+            if (m == 0) {
+                W[3][0] = wya[0] * va;
+                W[3][1] = wya[0] * vb;
+            } else if (m < 3 || (m == 3 && !k3y)) {
+                W[3][0] = W[3][0] + wya[m] * va;
+                W[3][1] = W[3][1] + wya[m] * vb;
+            }
+            if (m == 0) {
+                if (!dy) {
+                    W[3][2] = wyb[0] * va;
+                    W[3][3] = wyb[0] * vb;
+                }
+            } else {
+                const int t = dy ? m - 1 : m; // (wave-uniform)
+                const double w = dy ? wyb[m - 1] : wyb[m < 4 ? m : 3];
+                if (t == 0) {
+                    W[3][2] = w * va;
+                    W[3][3] = w * vb;
+                } else if (t < 3 || (t == 3 && !k3y)) {
+                    W[3][2] = W[3][2] + w * va;
+                    W[3][3] = W[3][3] + w * vb;
+                }
+            }
+        }
+        // the fine planes complete with coarse plane p (W[m] holds plane p - 3 + m)
+        while (z <= ze && cjc + (k3z ? 2 : 3) == p) {
+            if (okx && oka) {
+                double o[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++)
+                    o[q] = k3z ? (wz[0] * W[1][q] + wz[1] * W[2][q]) + wz[2] * W[3][q]
+                               : ((wz[0] * W[0][q] + wz[1] * W[1][q]) + wz[2] * W[2][q]) + wz[3] * W[3][q];
+                double* const q0 = frow + (int64_t)z * fldz;
+                store(q0, o[0], o[1]);
+                if (okb) store(q0 + fldy, o[2], o[3]);
+            }
+            z++;
+            cjc = cjn;
+            cjn = T.cj[2][zidx(z + 1)];
+#pragma unroll
+            for (int k = 0; k < 4; k++) wz[k] = T.cw[2][4 * zidx(z) + k];
+        }
+        __syncthreads();
+        cur = nxt;
+    }
+}
+
 } // namespace

@@ -22,6 +22,7 @@ import numpy as np
 from . import _abi
 from ._abi import GS_LINEAR, GS_MAX_WEIGHTS, GS_NEWTON, GS_NEWTON_B, GS_NEWTON_G, GS_NONLINEAR, gs_level, gs_params, gs_stencil, kernels, driver, diag  # noqa: F401
 from ._abi import GS_TRANSFER_POSITION, GS_TRANSFER_REFERENCE, gs_transfer_tables, transfer  # noqa: F401
+from ._abi import GS_FMG_PROLONG_ALIGNED, GS_FMG_PROLONG_POSITION, gs_fmg_tables  # noqa: F401
 
 CANONICAL_OFFSETS = [(0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)]
 
@@ -107,6 +108,7 @@ def _check(rc: int):
 
 
 _TRANSFERS = {"reference": GS_TRANSFER_REFERENCE, "position": GS_TRANSFER_POSITION}
+_FMG_PROLONGS = {"aligned": GS_FMG_PROLONG_ALIGNED, "position": GS_FMG_PROLONG_POSITION}
 FIELDS = {"v": 0, "restV": 1, "newtonV": 2, "f": 3, "r": 4, "newtonF": 5}
 
 
@@ -199,6 +201,21 @@ class HipGridData:
         m = driver().gs_grid_get_transfer(self.handle)
         return next(k for k, v in _TRANSFERS.items() if v == m)
 
+    def set_fmg_prolong(self, mode: str):
+        """Full multigrid's prolongation: "aligned" (the default: HipSolver.fmg needs sizes 2^k - 1) or "position"
+        (FMG starts at the coarsest level of every LINEAR / NONLINEAR single-GPU grid; transitions that are not
+        aligned take the tricubic prolongation by position, gs_fmg_prolong_pa, and need set_transfer("position");
+        aligned transitions, and so grids of sizes 2^k - 1, are unchanged bit for bit)."""
+        if mode not in _FMG_PROLONGS:
+            raise ValueError(f"fmg_prolong must be one of {sorted(_FMG_PROLONGS)}")
+        _check(driver().gs_grid_set_fmg_prolong(self.handle, _FMG_PROLONGS[mode]))
+
+    @property
+    def fmg_prolong(self) -> str:
+        """The FMG prolongation in force (set_fmg_prolong or GS_FMG_PROLONG): "aligned" or "position"."""
+        m = driver().gs_grid_get_fmg_prolong(self.handle)
+        return next(k for k, v in _FMG_PROLONGS.items() if v == m)
+
     def level_aligned(self, level: int) -> bool:
         """Whether the transition from `level` to `level + 1` is aligned (fine n = 2 coarse n + 1 on all three axes:
         the reference's transfers are exact there and POSITION mode changes nothing)."""
@@ -279,7 +296,8 @@ class HipSolver:
         """Full multigrid start: coarse right-hand sides restricted from level 0's f, the start level iterated from
         zero, every finer level from the tricubic prolongation of the level below, `cycles_per_level` V-cycles
         each. Overwrites v on every level; returns the level-0 residual norm. Raises GpuSolveError where FMG is
-        not applicable (sizes other than 2^k - 1, NEWTON mode, Z-slab grids, cycles_per_level < 1)."""
+        not applicable (sizes other than 2^k - 1 unless grid.set_fmg_prolong("position"), NEWTON mode, Z-slab
+        grids, cycles_per_level < 1)."""
         r = C.c_double()
         _check(driver().gs_grid_fmg(grid.handle, cycles_per_level, C.byref(r)))
         return r.value
@@ -335,6 +353,18 @@ def transfer_axis(nf: int):
     if rc:
         raise ValueError(kernels().gs_strerror(rc).decode())
     return {"pj": pj, "pt": pt, "rlo": rlo, "rcnt": rcnt, "rw": rw}
+
+
+def fmg_axis(nf: int):
+    """The tables of full multigrid's prolongation by position for one axis, fine nf -> coarse nf // 2 (gs_fmg_axis;
+    pure host code, no device needed): dict of cj (int32, nf + 2: the first of the K = 4 coarse nodes, K = 3 where
+    nf // 2 == 1) and cw ((nf + 2, 4): their Lagrange weights). ValueError for nf < 2."""
+    nf = int(nf)
+    cj, cw = np.zeros(max(nf, 0) + 2, np.int32), np.zeros((max(nf, 0) + 2, 4))
+    rc = transfer().gs_fmg_axis(nf, nf // 2, cj.ctypes.data_as(C.POINTER(C.c_int32)), cw.ctypes.data_as(_abi.dptr))
+    if rc:
+        raise ValueError(kernels().gs_strerror(rc).decode())
+    return {"cj": cj, "cw": cw}
 
 
 def field_layout(nx: int, ny: int, nz: int):

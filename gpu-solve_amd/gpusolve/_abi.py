@@ -21,6 +21,7 @@ GS_NEWTON_B = 3  # NEWTON with the precomputed linearisation factor B (include/g
 GS_NEWTON_G = 4  # GS_NEWTON_B whose factor field holds gamma everywhere (the first Newton iteration)
 GS_EINVAL = 100001
 GS_TRANSFER_REFERENCE, GS_TRANSFER_POSITION = 0, 1  # gs_grid_set_transfer (include/gpusolve_driver.h)
+GS_FMG_PROLONG_ALIGNED, GS_FMG_PROLONG_POSITION = 0, 1  # gs_grid_set_fmg_prolong (include/gpusolve_driver.h)
 GS_MAX_WEIGHTS = 8  # per-sweep relaxation weights per smoothing leg (include/gpusolve_hip.h)
 
 dptr = C.POINTER(C.c_double)
@@ -49,6 +50,11 @@ class gs_transfer_tables(C.Structure):
     """include/gpusolve_transfer.h: nf / nc per axis (host metadata), then device pointers per axis."""
     _fields_ = [("nf", i64 * 3), ("nc", i64 * 3), ("pj", C.c_void_p * 3), ("pt", C.c_void_p * 3),
                 ("rlo", C.c_void_p * 3), ("rcnt", C.c_void_p * 3), ("rw", C.c_void_p * 3)]
+
+
+class gs_fmg_tables(C.Structure):
+    """include/gpusolve_transfer.h: nf / nc per axis (host metadata), then device pointers per axis."""
+    _fields_ = [("nf", i64 * 3), ("nc", i64 * 3), ("cj", C.c_void_p * 3), ("cw", C.c_void_p * 3)]
 
 
 # name -> (restype, argtypes); void* is used for device pointers and streams
@@ -168,6 +174,9 @@ TRANSFER_API = {
     "gs_residual_restrict_pa": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int, C.c_double, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(gs_level),
                                           C.POINTER(gs_transfer_tables), C.c_void_p]),
+    "gs_fmg_axis": (C.c_int, [i64, i64, C.POINTER(C.c_int32), dptr]),
+    "gs_fmg_prolong_pa": (C.c_int, [C.c_void_p, C.POINTER(gs_level), C.c_void_p, C.POINTER(gs_level),
+                                    C.POINTER(gs_fmg_tables), C.c_void_p]),
 }
 
 DRIVER_API = {
@@ -181,6 +190,8 @@ DRIVER_API = {
     "gs_grid_fmg_start_level": (C.c_int, [C.c_void_p]),
     "gs_grid_set_transfer": (C.c_int, [C.c_void_p, C.c_int]),
     "gs_grid_get_transfer": (C.c_int, [C.c_void_p]),
+    "gs_grid_set_fmg_prolong": (C.c_int, [C.c_void_p, C.c_int]),
+    "gs_grid_get_fmg_prolong": (C.c_int, [C.c_void_p]),
     "gs_grid_level_aligned": (C.c_int, [C.c_void_p, C.c_int]),
     "gs_grid_set_weights": (C.c_int, [C.c_void_p, dptr, C.c_int, dptr, C.c_int]),
     "gs_grid_get_weights": (C.c_int, [C.c_void_p, dptr, dptr]),

@@ -109,13 +109,26 @@ int gs_parse_omegas(const char* text, int pre, int post, double* out);
  * ordinary sweeps; the tiled steps, the fused prolongation pairs and the one-launch coarse cycle are not taken there),
  * aligned transitions are unchanged launch for launch: on sizes 2^k - 1 the two modes give the same bits. Applies to
  * gs_grid_solve in all three modes, gs_grid_vcycle and gs_grid_vcycle_level; gs_grid_fmg keeps its alignment
- * requirement in either mode. The tables of the non-aligned transitions are built and uploaded when POSITION is first
+ * requirement in either mode unless gs_grid_set_fmg_prolong lifts it (below). The tables of the non-aligned transitions are built and uploaded when POSITION is first
  * switched on. Fails (return 1, gs_last_error(), nothing changed) for any other mode value and for POSITION on a
  * Z-slab / RCCL grid. GS_TRANSFER=position|reference in the environment when the grid is created sets the mode; any
  * other value fails the creation. */
 enum { GS_TRANSFER_REFERENCE = 0, GS_TRANSFER_POSITION = 1 };
 int gs_grid_set_transfer(void* grid, int mode);
 int gs_grid_get_transfer(void* grid);
+/* Full multigrid's prolongation (added; DESIGN.md §4.7 "FMG on every size"). GS_FMG_PROLONG_ALIGNED, the default:
+ * gs_grid_fmg as described above, unchanged launch for launch. GS_FMG_PROLONG_POSITION: gs_grid_fmg_start_level is the
+ * coarsest level on every LINEAR / NONLINEAR single-GPU grid (NEWTON, Z-slab and trace grids: still 0, still refused);
+ * f is restricted by gs_restrict_pa and v prolonged by gs_fmg_prolong_pa (gpusolve_transfer.h: the tricubic operator by
+ * position) on every transition that is not aligned, aligned transitions keep gs_restrict / gs_fmg_prolong — on a grid
+ * whose transitions are all aligned the setting changes nothing, bit for bit. A grid with a non-aligned transition
+ * must also run the POSITION transfers (gs_grid_set_transfer): otherwise gs_grid_fmg fails with nothing done. The
+ * tables are built and uploaded when POSITION is first set. Fails (return 1, gs_last_error(), nothing changed) for any
+ * other mode value. GS_FMG_PROLONG=position|aligned in the environment when the grid is created sets the mode; any
+ * other value fails the creation. */
+enum { GS_FMG_PROLONG_ALIGNED = 0, GS_FMG_PROLONG_POSITION = 1 };
+int gs_grid_set_fmg_prolong(void* grid, int mode);
+int gs_grid_get_fmg_prolong(void* grid);
 /* 1 if the transition from `level` to `level + 1` is aligned (fine n = 2 coarse n + 1 on all three axes), 0 if not,
  * -1 if there is no such transition. */
 int gs_grid_level_aligned(void* grid, int level);

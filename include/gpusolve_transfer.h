@@ -73,6 +73,36 @@ int gs_residual_restrict_pa(const gs_stencil* S, const gs_level* fl, int mode, d
                             const double* f, const double* w, double* coarse_f, const gs_level* cl,
                             const gs_transfer_tables* T, hipStream_t stream);
 
+/* ---- Full multigrid's prolongation of a SOLUTION by position (gs_fmg_prolong's role on transitions that are not
+ * aligned). Tricubic, separable, X then Y then Z. Per axis, with q, pj, rem, D as above and
+ * P = m + 2 the number of padded coarse values:
+ *     P >= 4: K = 4, cj[i] = clamp(pj - 1, 0, P - 4);      P = 3 (m = 1): K = 3, cj[i] = 0
+ *     t = (double)(pj - cj[i]) + (double)rem / (double)D      the point's coordinate in the nodes cj .. cj + K - 1
+ * and the Lagrange weights, each evaluated in double as written, left to right:
+ *     K = 4: w0 = -(((t-1)*(t-2))*(t-3))/6   w1 = ((t*(t-2))*(t-3))/2   w2 = -((t*(t-1))*(t-3))/2   w3 = ((t*(t-1))*(t-2))/6
+ *     K = 3: w0 = ((t-1)*(t-2))/2            w1 = -(t*(t-2))            w2 = (t*(t-1))/2            w3 = 0.0
+ * The axis value is  ((w0 * c[cj] + w1 * c[cj+1]) + w2 * c[cj+2]) + w3 * c[cj+3]  truncated to K terms, the first
+ * product starting the sum, no contraction. The coarse ring takes part as data; only interior fine points are written;
+ * no read leaves the padded coarse box. On an aligned axis this is gs_fmg_prolong's cubic up to rounding (not bit for
+ * bit: the weights are evaluated, not the constants 5/16, 15/16, ...).
+ *
+ * gs_fmg_axis fills HOST arrays for one axis: cj, nf + 2 entries, and cw, 4 * (nf + 2) doubles (w0..w3 of fine index
+ * i at cw[4 * i]); entries 0 and nf + 1 are zero. gs_fmg_tables describes uploaded copies as gs_transfer_tables does. */
+typedef struct {
+    int64_t nf[3], nc[3]; /* per axis (x, y, z): the transition the arrays were built for */
+    const int32_t* cj[3]; /* device pointers */
+    const double* cw[3];
+} gs_fmg_tables;
+
+/* Pure host code (no device). GS_EINVAL, with nothing written, unless nf >= 2, nc == nf / 2 and both pointers are
+ * non-null. */
+int gs_fmg_axis(int64_t nf, int64_t nc, int32_t* cj, double* cw);
+
+/* fine interior = P coarse (whole levels; any transition with coarse = fine / 2 per axis, aligned axes included).
+ * The launchers' conventions and layout contract above. */
+int gs_fmg_prolong_pa(const double* coarse, const gs_level* cl, double* fine, const gs_level* fl,
+                      const gs_fmg_tables* T, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
