@@ -23,6 +23,7 @@
 
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 
 #include "gpusolve_hip.h"
@@ -2225,7 +2226,6 @@ bool bad_level(const gs_level* L)
            L->nx > INT32_MAX / 2 || L->ny > INT32_MAX / 2 || L->nz > INT32_MAX / 2;
 }
 
-// Dispatch a stencil pass over (mode, kind) to the fast or the generic kernel.
 // ---------------------------------------------------------------------------------------------
 // Two fused Jacobi sweeps (temporal blocking): out = S(S(v)) reading v and f once and writing once
 // (24 B per two lattice updates instead of 48). Wavefront along z: at step z the block computes
@@ -3241,6 +3241,33 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
     }
 }
 
+// Run-time selectors as compile-time constants, for the launchers' choice of a kernel instance:
+// with_bools(f, b...) calls f(std::bool_constant<b>{}...), with_mode(f, mode, b...) the same behind the mode's
+// std::integral_constant (mode: a base mode the caller has range-checked). f is a generic lambda that names the
+// instance; a combination that has no instance is excluded there with `if constexpr`, so none is built for it.
+template <class F>
+auto with_bools(F&& f)
+{
+    return f();
+}
+template <class F, class... B>
+auto with_bools(F&& f, bool b, B... bs)
+{
+    return b ? with_bools([&](auto... c) { return f(std::true_type{}, c...); }, bs...)
+             : with_bools([&](auto... c) { return f(std::false_type{}, c...); }, bs...);
+}
+template <class F, class... B>
+auto with_mode(F&& f, int mode, B... bs)
+{
+    if (mode == GS_LINEAR)
+        return with_bools([&](auto... c) { return f(std::integral_constant<int, GS_LINEAR>{}, c...); }, bs...);
+    if (mode == GS_NONLINEAR)
+        return with_bools([&](auto... c) { return f(std::integral_constant<int, GS_NONLINEAR>{}, c...); }, bs...);
+    if (mode == GS_NEWTON_B)
+        return with_bools([&](auto... c) { return f(std::integral_constant<int, GS_NEWTON_B>{}, c...); }, bs...);
+    return with_bools([&](auto... c) { return f(std::integral_constant<int, GS_NEWTON>{}, c...); }, bs...);
+}
+
 // Blocks of `threads` threads kernel `fn` keeps resident on the whole GPU (occupancy x CUs, cached).
 int64_t resident_blocks(const void* fn, int threads)
 {
@@ -3312,18 +3339,24 @@ int64_t device_cus()
 // Geometry rule of the fused pair: the whole x-row in one block (or, XH, one column block of 512
 // points) and enough work for >= 128 blocks of 4-plane chunks; the z-chunk is then chosen for >= 1024
 // blocks (4..64 planes: at 512^3, 64-plane chunks measured 5-8% faster than 32 — fewer re-read
-// chunk-boundary planes). Returns 0 (impossible), 1 (possible) or 2 (possible and fills the GPU);
-// *y2: the k_tb2y whole-row shape, *xh: the k_tb2y column-block shape (rows of more than 512 points, up to
-// 2^20; always one of the two).
-int tb2_plan(const gs_stencil* S, const gs_level* L, int* zc, dim3* grid, dim3* block, bool* y2 = nullptr,
-             int mode = GS_LINEAR, bool* xh = nullptr)
+// chunk-boundary planes). fills: 0 (impossible), 1 (possible) or 2 (possible and fills the GPU);
+// colb: the k_tb2y column-block shape (XH: rows of more than 512 points, up to 2^20), else its whole-row shape.
+struct PairPlan {
+    int fills;
+    int zc;
+    dim3 grid, block;
+    bool colb;
+};
+
+PairPlan tb2_plan(const gs_stencil* S, const gs_level* L, int mode = GS_LINEAR)
 {
-    if (!S || !L || !canonical_order(S) || L->nx < 1 || L->ny < 1 || L->nz < 1) return 0;
+    const PairPlan none{0, 0, dim3(1), dim3(1), false};
+    if (!S || !L || !canonical_order(S) || L->nx < 1 || L->ny < 1 || L->nz < 1) return none;
     const bool two = L->nx <= 2 * WAVE * TBY_WX;
     // longer rows: column blocks in every mode (NEWTON since r04: sweep 2's rows in LDS, edge values loaded
     // per step: 255 VGPRs, no spill; profiles/r04/r04i_newton_1023.txt)
     const bool colb = !two;
-    if (colb && L->nx > (int64_t)1 << 20) return 0;
+    if (colb && L->nx > (int64_t)1 << 20) return none;
     const int64_t nh = colb ? (L->nx + 2 * WAVE * TBY_WX - 1) / (2 * WAVE * TBY_WX) : 1;
     const int rows = 2 * (newtonish(mode) ? TBY_RY_NEWTON : TBY_RY); // output rows per block
     const int64_t tiles = (L->ny + rows - 1) / rows * nh;
@@ -3376,12 +3409,32 @@ int tb2_plan(const gs_stencil* S, const gs_level* L, int* zc, dim3* grid, dim3* 
     }
     if (kKnobs.midZc > 0 && L->z0 == 0 && L->nx * L->ny * L->nz < ((int64_t)1 << 26)) c = std::max(2, kKnobs.midZc);
     c &= ~(int64_t)1; // even: every chunk starts on an odd plane (the fused prolongation's parities)
-    *zc = (int)c;
-    *grid = dim3((unsigned)tiles, (unsigned)((L->nz + c - 1) / c));
-    *block = dim3(WAVE, colb ? (unsigned)TBY_WX : (unsigned)((L->nx + 2 * WAVE - 1) / (2 * WAVE)), 2);
-    if (y2) *y2 = two;
-    if (xh) *xh = colb;
-    return fills;
+    return PairPlan{fills, (int)c, dim3((unsigned)tiles, (unsigned)((L->nz + c - 1) / c)),
+                    dim3(WAVE, colb ? (unsigned)TBY_WX : (unsigned)((L->nx + 2 * WAVE - 1) / (2 * WAVE)), 2), colb};
+}
+
+// k_tb2y's signature, and the one place that writes its argument list: kernel `fn` (an instance of the launcher's
+// selector, or one of the diagnostics' variants) over plan `p`. PairOperands: what the plain pairs leave empty — the
+// prolongation pairs' coarse iterate and subtrahend (from the plane under fine local plane 0), the coarse level's
+// extents and pitches, and `es`, their edge-column workspace (diagnostics: the timestamp buffer).
+using PairKernel = void (*)(Coef, const double*, const double*, const double*, double*, double*, int, int, int, int64_t,
+                            int64_t, int, int, int, const double*, const double*, int, int, int, int64_t, int64_t,
+                            const double*);
+struct PairOperands {
+    const double *pc, *ps;
+    int cnx, cny, cnz;
+    int64_t cldy, cldz;
+    const double* es;
+};
+
+int launch_tb2y(PairKernel fn, const PairPlan& p, const Coef& k, const gs_level* L, const double* v_in, const double* f,
+                const double* w, double* v_out, double* partials, int zlo, int zhi, hipStream_t st,
+                const PairOperands& o = PairOperands{})
+{
+    hipLaunchKernelGGL(fn, p.grid, p.block, 0, st, k, v_in, f, w, v_out, partials, (int)L->nx, (int)L->ny, (int)L->nz,
+                       L->ldy, L->ldz, p.zc, zlo ? 1 : 0, zhi ? 1 : 0, o.pc, o.ps, o.cnx, o.cny, o.cnz, o.cldy, o.cldz,
+                       o.es);
+    return launch_status();
 }
 
 // Production shape of the register-blocked kernel (chosen by tools/kbench.py on MI355X,
@@ -3419,6 +3472,7 @@ PassPlan pass_plan(const gs_stencil* S, const gs_level* L)
     return p;
 }
 
+// Dispatch a stencil pass over (mode, kind) to the fast or the generic kernel.
 template <int KIND, bool ADD>
 int launch_pass(const gs_stencil* S, const gs_level* L, int mode, double omega, double gamma, const double* v,
                 const double* f, const double* w, double* out, double* partials, hipStream_t st)
@@ -3434,31 +3488,20 @@ int launch_pass(const gs_stencil* S, const gs_level* L, int mode, double omega, 
     const PassPlan plan = pass_plan(S, L);
     if (plan.rb) {
         const dim3 g = plan.grid, b(WAVE, RB_W);
-#define GS_RBU(M, Z, U) hipLaunchKernelGGL((k_rb<M, KIND, ADD, RB_RY, RB_W, true, RB_NT, false, false, Z, U>), g, b, 0, st, k, v, f, w, out, partials, nx, ny, nz, L->ldy, L->ldz, plan.zc)
-#define GS_RB(M, Z) do { if (k.unit) GS_RBU(M, Z, true); else GS_RBU(M, Z, false); } while (0)
-        if (!v) {
-            if constexpr (KIND == 0 && !ADD) {
-                if (mode == GS_LINEAR) GS_RB(GS_LINEAR, true);
-                else if (mode == GS_NEWTON_B) GS_RB(GS_NEWTON_B, true);
-                else GS_RB(GS_NEWTON, true);
-            }
-        } else if constexpr (KIND == 2) {
-            GS_RB(GS_NONLINEAR, false); // the FAS operator (NONLINEAR only)
-        } else if (mode == GS_LINEAR) GS_RB(GS_LINEAR, false);
-        else if (mode == GS_NONLINEAR) GS_RB(GS_NONLINEAR, false);
-        else if (mode == GS_NEWTON_B) GS_RB(GS_NEWTON_B, false);
-        else GS_RB(GS_NEWTON, false);
-#undef GS_RB
-#undef GS_RBU
+        // k_rb per (mode, zero iterate, unit stencil): the zero iterate for sweeps outside NONLINEAR, KIND 2 (the FAS
+        // operator) for NONLINEAR only, as checked above
+        with_mode([&](auto M, auto Z, auto U) {
+            if constexpr ((!Z || (KIND == 0 && !ADD && M != GS_NONLINEAR)) && (KIND != 2 || M == GS_NONLINEAR))
+                hipLaunchKernelGGL((k_rb<M, KIND, ADD, RB_RY, RB_W, true, RB_NT, false, false, Z, U>), g, b, 0, st, k, v,
+                                   f, w, out, partials, nx, ny, nz, L->ldy, L->ldz, plan.zc);
+        }, mode, !v, k.unit);
     } else {
         const dim3 g = plan.grid, b(GN_BX, GN_BY);
-#define GS_GN(M) hipLaunchKernelGGL((k_generic<M, KIND, ADD>), g, b, 0, st, k, v, f, w, out, partials, nx, ny, nz, L->ldy, L->ldz)
-        if constexpr (KIND == 2) GS_GN(GS_NONLINEAR);
-        else if (mode == GS_LINEAR) GS_GN(GS_LINEAR);
-        else if (mode == GS_NONLINEAR) GS_GN(GS_NONLINEAR);
-        else if (mode == GS_NEWTON_B) GS_GN(GS_NEWTON_B);
-        else GS_GN(GS_NEWTON);
-#undef GS_GN
+        with_mode([&](auto M) {
+            if constexpr (KIND != 2 || M == GS_NONLINEAR)
+                hipLaunchKernelGGL((k_generic<M, KIND, ADD>), g, b, 0, st, k, v, f, w, out, partials, nx, ny, nz, L->ldy,
+                                   L->ldz);
+        }, mode);
     }
     return launch_status();
 }

@@ -639,8 +639,7 @@ int gs_debug_sweep_variant(int variant, const gs_stencil* S, const gs_level* L, 
 struct PairVariant {
     const char* name;
     int ry, wxmax, wy;
-    void (*kern)(Coef, const double*, const double*, const double*, double*, double*, int, int, int, int64_t,
-                 int64_t, int, int, int, const double*, const double*, int, int, int, int64_t, int64_t, const double*);
+    PairKernel kern;
 };
 #define GS_PVY(RY, NTF, SPEC, TAG) {"tb2y ry" #RY " wx4 wy2" TAG, RY, 4, 2, k_tb2y<GS_LINEAR, RY, 4, true, NTF, false, SPEC>}
 const PairVariant kPairVariants[] = {GS_PVY(2, false, false, " f-cached"),
@@ -676,10 +675,9 @@ int gs_debug_pair_variant(int variant, const gs_stencil* S, const gs_level* L, d
         zc = (int)(c < 4 ? 4 : (c > 32 ? 32 : c));
     }
     const Coef k = make_coef(S, L, omega, 0.0);
-    hipLaunchKernelGGL(V.kern, dim3((unsigned)tiles, (unsigned)((L->nz + zc - 1) / zc)), dim3(WAVE, (unsigned)wx, V.wy), 0,
-                       st, k, v_in, f, nullptr, v_out, nullptr, (int)L->nx, (int)L->ny, (int)L->nz, L->ldy, L->ldz, zc,
-                       0, 0, nullptr, nullptr, 0, 0, 0, (int64_t)0, (int64_t)0, nullptr);
-    return launch_status();
+    const PairPlan plan{1, zc, dim3((unsigned)tiles, (unsigned)((L->nz + zc - 1) / zc)), dim3(WAVE, (unsigned)wx, V.wy),
+                        false};
+    return launch_tb2y(V.kern, plan, k, L, v_in, f, nullptr, v_out, nullptr, 0, 0, st);
 }
 
 // The production LINEAR pair (k_tb2y, PFD 2, plan of gs_jacobi_sweep2 unless zc > 0) with a per-block
@@ -688,22 +686,19 @@ int gs_debug_pair_variant(int variant, const gs_stencil* S, const gs_level* L, d
 int gs_debug_pair_timestamps(const gs_stencil* S, const gs_level* L, double omega, const double* v_in, double* v_out,
                              const double* f, int zc, double* ts, hipStream_t st)
 {
-    int zcp;
-    dim3 g, b;
-    bool y2 = false, xh = false;
-    if (!S || bad_level(L) || !valid_stencil(S) || !v_in || !v_out || !f || !ts || v_in == v_out || zc < 0 ||
-        !tb2_plan(S, L, &zcp, &g, &b, &y2, GS_LINEAR, &xh) || !y2)
+    if (!S || bad_level(L) || !valid_stencil(S) || !v_in || !v_out || !f || !ts || v_in == v_out || zc < 0)
         return GS_EINVAL;
+    PairPlan plan = tb2_plan(S, L, GS_LINEAR);
+    if (!plan.fills || plan.colb) return GS_EINVAL;
     if (zc > 0) {
-        zcp = zc;
-        g.y = (unsigned)((L->nz + zc - 1) / zc);
+        plan.zc = zc;
+        plan.grid.y = (unsigned)((L->nz + zc - 1) / zc);
     }
     const Coef k = make_coef(S, L, omega, 0.0);
-#define GS_TSP(U) hipLaunchKernelGGL((k_tb2y<GS_LINEAR, TBY_RY, TBY_WX, true, false, false, true, 0, 2, false, U, true>), g, b, 0, st, k, v_in, f, nullptr, v_out, nullptr, (int)L->nx, (int)L->ny, (int)L->nz, L->ldy, L->ldz, zcp, 0, 0, nullptr, nullptr, 0, 0, 0, (int64_t)0, (int64_t)0, ts)
-    if (k.unit) GS_TSP(true);
-    else GS_TSP(false);
-#undef GS_TSP
-    return launch_status();
+    const PairKernel fn = k.unit ? k_tb2y<GS_LINEAR, TBY_RY, TBY_WX, true, false, false, true, 0, 2, false, true, true>
+                                 : k_tb2y<GS_LINEAR, TBY_RY, TBY_WX, true, false, false, true, 0, 2, false, false, true>;
+    return launch_tb2y(fn, plan, k, L, v_in, f, nullptr, v_out, nullptr, 0, 0, st,
+                       PairOperands{nullptr, nullptr, 0, 0, 0, 0, 0, ts});
 }
 
 // Timing only: the production LINEAR pair marching the planes in descending order (reverse != 0: every
@@ -714,25 +709,21 @@ int gs_debug_pair_timestamps(const gs_stencil* S, const gs_level* L, double omeg
 int gs_debug_pair_reverse(const gs_stencil* S, const gs_level* L, double omega, const double* v_in, double* v_out,
                           const double* f, int reverse, hipStream_t st)
 {
-    int zc;
-    dim3 g, b;
-    bool y2 = false, xh = false;
-    if (!S || bad_level(L) || !valid_stencil(S) || !v_in || !v_out || !f || v_in == v_out ||
-        !tb2_plan(S, L, &zc, &g, &b, &y2, GS_LINEAR, &xh) || !y2)
-        return GS_EINVAL;
+    if (!S || bad_level(L) || !valid_stencil(S) || !v_in || !v_out || !f || v_in == v_out) return GS_EINVAL;
+    const PairPlan plan = tb2_plan(S, L, GS_LINEAR);
+    if (!plan.fills || plan.colb) return GS_EINVAL;
     const Coef k = make_coef(S, L, omega, 0.0);
-    const int64_t sh = (reverse & 1) ? (L->nz + 1) * L->ldz : 0, ldz = (reverse & 1) ? -L->ldz : L->ldz;
-#define GS_RVP(U, NT) hipLaunchKernelGGL((k_tb2y<GS_LINEAR, TBY_RY, TBY_WX, NT, false, false, true, 0, 2, false, U>), g, b, 0, st, k, v_in + sh, f + sh, nullptr, v_out + sh, nullptr, (int)L->nx, (int)L->ny, (int)L->nz, L->ldy, ldz, zc, 0, 0, nullptr, nullptr, 0, 0, 0, (int64_t)0, (int64_t)0, nullptr)
-    // reverse bit 1: ordinary (not non-temporal) stores of the output
-    if (reverse & 2) {
-        if (k.unit) GS_RVP(true, false);
-        else GS_RVP(false, false);
-    } else {
-        if (k.unit) GS_RVP(true, true);
-        else GS_RVP(false, true);
-    }
-#undef GS_RVP
-    return launch_status();
+    const int64_t sh = (reverse & 1) ? (L->nz + 1) * L->ldz : 0;
+    gs_level R = *L; // the level seen through the negative plane pitch
+    if (reverse & 1) R.ldz = -L->ldz;
+    // [reverse bit 1: ordinary (not non-temporal) stores of the output][unit stencil]
+    static const PairKernel tab[2][2] = {
+        {k_tb2y<GS_LINEAR, TBY_RY, TBY_WX, true, false, false, true, 0, 2, false, false>,
+         k_tb2y<GS_LINEAR, TBY_RY, TBY_WX, true, false, false, true, 0, 2, false, true>},
+        {k_tb2y<GS_LINEAR, TBY_RY, TBY_WX, false, false, false, true, 0, 2, false, false>,
+         k_tb2y<GS_LINEAR, TBY_RY, TBY_WX, false, false, false, true, 0, 2, false, true>}};
+    return launch_tb2y(tab[(reverse & 2) != 0][k.unit != 0], plan, k, &R, v_in + sh, f + sh, nullptr, v_out + sh, nullptr,
+                       0, 0, st);
 }
 
 // The LINEAR pair (k_tb2y, whole 512-point rows) in other row / prefetch / occupancy shapes (r06, verdict r05 item 2):
@@ -747,31 +738,26 @@ int gs_debug_pair_shape(const gs_stencil* S, const gs_level* L, double omega, co
         (wpe != 0 && wpe != 3 && wpe != 4))
         return GS_EINVAL;
     const Coef k = make_coef(S, L, omega, 0.0);
-    const dim3 g((unsigned)((L->ny + 2 * ry - 1) / (2 * ry)), (unsigned)((L->nz + zc - 1) / zc)),
-        b(WAVE, (unsigned)((L->nx + 2 * WAVE - 1) / (2 * WAVE)), 2);
-    using K = void (*)(Coef, const double*, const double*, const double*, double*, double*, int, int, int, int64_t,
-                       int64_t, int, int, int, const double*, const double*, int, int, int, int64_t, int64_t,
-                       const double*);
+    const PairPlan plan{1, zc, dim3((unsigned)((L->ny + 2 * ry - 1) / (2 * ry)), (unsigned)((L->nz + zc - 1) / zc)),
+                        dim3(WAVE, (unsigned)((L->nx + 2 * WAVE - 1) / (2 * WAVE)), 2), false};
 #define GS_PSH(RY, P, W) k_tb2y<GS_LINEAR, RY, TBY_WX, true, false, false, true, 0, P, false, true, false, W>
-    static const K tab[2][2][3] = {{{GS_PSH(1, 1, 0), GS_PSH(1, 1, 3), GS_PSH(1, 1, 4)},
-                                    {GS_PSH(1, 2, 0), GS_PSH(1, 2, 3), GS_PSH(1, 2, 4)}},
-                                   {{GS_PSH(2, 1, 0), GS_PSH(2, 1, 3), GS_PSH(2, 1, 4)},
-                                    {GS_PSH(2, 2, 0), GS_PSH(2, 2, 3), GS_PSH(2, 2, 4)}}};
+    static const PairKernel tab[2][2][3] = {{{GS_PSH(1, 1, 0), GS_PSH(1, 1, 3), GS_PSH(1, 1, 4)},
+                                             {GS_PSH(1, 2, 0), GS_PSH(1, 2, 3), GS_PSH(1, 2, 4)}},
+                                            {{GS_PSH(2, 1, 0), GS_PSH(2, 1, 3), GS_PSH(2, 1, 4)},
+                                             {GS_PSH(2, 2, 0), GS_PSH(2, 2, 3), GS_PSH(2, 2, 4)}}};
 #undef GS_PSH
     if (!k.unit) return GS_EINVAL; // (the unit-stencil sums only: every reference config)
-    hipLaunchKernelGGL(tab[ry - 1][pfd - 1][wpe == 0 ? 0 : (wpe == 3 ? 1 : 2)], g, b, 0, st, k, v_in, f, nullptr, v_out,
-                       nullptr, (int)L->nx, (int)L->ny, (int)L->nz, L->ldy, L->ldz, zc, 0, 0, nullptr, nullptr, 0, 0,
-                       0, (int64_t)0, (int64_t)0, nullptr);
-    return launch_status();
+    return launch_tb2y(tab[ry - 1][pfd - 1][wpe == 0 ? 0 : (wpe == 3 ? 1 : 2)], plan, k, L, v_in, f, nullptr, v_out, nullptr,
+                       0, 0, st);
 }
 
 int64_t gs_debug_pair_blocks(const gs_stencil* S, const gs_level* L, int zc)
 {
-    int zcp;
-    dim3 g, b;
-    if (!S || bad_level(L) || !valid_stencil(S) || !tb2_plan(S, L, &zcp, &g, &b, nullptr, GS_LINEAR)) return 0;
-    if (zc > 0) g.y = (unsigned)((L->nz + zc - 1) / zc);
-    return (int64_t)g.x * g.y;
+    if (!S || bad_level(L) || !valid_stencil(S)) return 0;
+    PairPlan plan = tb2_plan(S, L, GS_LINEAR);
+    if (!plan.fills) return 0;
+    if (zc > 0) plan.grid.y = (unsigned)((L->nz + zc - 1) / zc);
+    return (int64_t)plan.grid.x * plan.grid.y;
 }
 
 int gs_debug_bw(int kind, int unroll, int nt, int blocks, double* out, const double* a, const double* b, int64_t n,

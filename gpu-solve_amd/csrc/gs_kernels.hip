@@ -3,6 +3,75 @@
 // bandwidth probes, the rejected k_prr) live in gs_diag.hip -> libgpusolve_diag.so.
 #include "gs_device.hpp"
 
+namespace {
+
+// The product's instance of the fused pair k_tb2y for what a launch knows: the base mode, a zero iterate (zv), column
+// blocks (colb, else whole rows), the unit stencil, FX (rows of whole waves: no per-lane range selects), a prolongation
+// pair (pro, else a plain pair) and, of the NEWTON prolongation pairs, the instance sized for two x-waves (wx2). The
+// only place that spells the kernel's template arguments: `plain` and `prolong` list the 51 instances that exist
+// (DESIGN.md §9), any other combination has none (nullptr).
+PairKernel tb2y_kernel(int mode, bool zv, bool colb, bool unit, bool fx, bool pro, bool wx2)
+{
+    return with_mode([](auto M, auto ZV, auto XH, auto UN, auto FX, auto PRO, auto WX2) -> PairKernel {
+        // the product's fixed choices (libgpusolve_diag.so varies them): non-temporal output stores, cached f loads,
+        // per-wave-row code, no timestamps, the default register allocation (one wave per SIMD allowed)
+        constexpr bool NT = true, NTF = false, SPEC = true, TS = false;
+        constexpr int WPE = 0;
+        constexpr int RY = newtonish(M) ? TBY_RY_NEWTON : TBY_RY, WXMAX = WX2 ? 2 : TBY_WX;
+        // tby_pfd's prefetch distance; one step for the prolongation pairs and the zero-iterate column blocks
+        constexpr int PFD = (PRO || (XH && ZV)) ? 1 : tby_pfd(M);
+        // plain pairs: every mode in both shapes, a zero iterate outside NONLINEAR; FX for the unit stencil's LINEAR
+        // pairs and NEWTON_B's whole-row pair
+        constexpr bool plain = !PRO && !WX2 && !(ZV && M == GS_NONLINEAR) &&
+                               (!FX || (UN && !ZV && (M == GS_LINEAR || (M == GS_NEWTON_B && !XH))));
+        // prolongation pairs: LINEAR and NEWTON in both shapes, NEWTON's whole rows for two x-waves too; FX for the
+        // unit stencil's LINEAR / NEWTON_B pairs of four x-waves
+        constexpr bool prolong = PRO && !ZV && (M == GS_LINEAR || newtonish(M)) &&
+                                 (!WX2 || (newtonish(M) && !XH && !FX)) &&
+                                 (!FX || (UN && (M == GS_LINEAR || M == GS_NEWTON_B)));
+        if constexpr (plain || prolong)
+            return k_tb2y<M, RY, WXMAX, NT, NTF, ZV, SPEC, PRO ? 1 : 0, PFD, XH, UN, TS, WPE, FX>;
+        else
+            return nullptr;
+    }, mode, zv, colb, unit, fx, pro, wx2);
+}
+
+// The prolongation pair's plan (fills = 0: unsupported): LINEAR and NEWTON (NONLINEAR carries restV too). Rows of more
+// than 512 points (column blocks, XH, NEWTON too since r04) with the workspace of prolong_ws_elems (the corrected edge
+// columns). The fine planes' parities must be the global ones (even z0): they select each plane's combination
+PairPlan prolong_plan(const gs_stencil* S, const gs_level* L, int mode)
+{
+    if (bad_level(L) || !valid_stencil(S) || !(mode == GS_LINEAR || newtonish(mode)) || L->z0 % 2 != 0) return PairPlan{};
+    return tb2_plan(S, L, mode);
+}
+
+int64_t prolong_ws_elems(const gs_level* L, const PairPlan& plan)
+{
+    if (!plan.fills || !plan.colb) return 0;
+    const int64_t bw = 2 * WAVE * TBY_WX, nb = (L->nx + bw - 1) / bw - 1; // interior block boundaries
+    return nb * (L->nz + 4) * 4 * (L->ny + 2);
+}
+
+// The NEWTON update + compF pass k_newton_upd per (unit stencil, + the level-1 restriction to coarse_w on `cl`, + the
+// next factor B to b_out) over pass_plan's grid: the grid and partial layout of gs_newton_F (k_rb KIND 1)
+int launch_newton_upd(const gs_stencil* S, const gs_level* L, double gamma, const double* w, const double* e,
+                      const double* F, double* w_out, double* f, double* partials, double* coarse_w, const gs_level* cl,
+                      double* b_out, hipStream_t st)
+{
+    const Coef k = make_coef(S, L, 0.0, gamma);
+    const PassPlan plan = pass_plan(S, L);
+    const gs_level c = cl ? *cl : gs_level{};
+    with_bools([&](auto U, auto RS, auto BF) {
+        if constexpr (RS || !BF)
+            hipLaunchKernelGGL((k_newton_upd<RB_RY, RB_W, U, RS, BF>), plan.grid, dim3(WAVE, RB_W), 0, st, k, w, e, F,
+                               w_out, f, partials, (int)L->nx, (int)L->ny, (int)L->nz, L->ldy, L->ldz, plan.zc, coarse_w,
+                               (int)c.nx, (int)c.ny, (int)c.nz, c.ldy, c.ldz, b_out);
+    }, k.unit, cl != nullptr, b_out != nullptr);
+    return launch_status();
+}
+
+} // namespace
+
 // =============================================================================================
 extern "C" {
 
@@ -49,11 +118,9 @@ int gs_jacobi_sweep_norm(const gs_stencil* S, const gs_level* L, int mode, doubl
 
 int gs_jacobi_sweep2_supported_mode(const gs_stencil* S, const gs_level* L, int mode)
 {
-    int zc;
-    dim3 g, b;
     mode = base_mode(mode);
     if (mode < GS_LINEAR || mode > GS_NEWTON_B) return 0;
-    return (!bad_level(L) && valid_stencil(S)) ? tb2_plan(S, L, &zc, &g, &b, nullptr, mode) : 0;
+    return (!bad_level(L) && valid_stencil(S)) ? tb2_plan(S, L, mode).fills : 0;
 }
 
 int gs_jacobi_sweep2_supported(const gs_stencil* S, const gs_level* L)
@@ -82,22 +149,20 @@ int gs_jacobi_sweep2_w(const gs_stencil* S, const gs_level* L, int mode, const d
 
 const char* gs_jacobi_sweep2_kernel(const gs_stencil* S, const gs_level* L, int mode)
 {
-    int zc;
-    dim3 g, b;
-    bool y2 = false, xh = false;
     mode = base_mode(mode);
-    if (bad_level(L) || !valid_stencil(S) || !tb2_plan(S, L, &zc, &g, &b, &y2, mode, &xh)) return "";
-    if (y2) return "k_tb2y: 4x2 waves, 2 rows per wave, LDS halo-row exchange, per-wave-row code";
+    if (bad_level(L) || !valid_stencil(S)) return "";
+    const PairPlan plan = tb2_plan(S, L, mode);
+    if (!plan.fills) return "";
+    if (!plan.colb) return "k_tb2y: 4x2 waves, 2 rows per wave, LDS halo-row exchange, per-wave-row code";
     return "k_tb2y XH: 512-point column blocks of 4x2 waves, edge columns computed lane-parallel";
 }
 
 int64_t gs_jacobi_sweep2_num_partials(const gs_stencil* S, const gs_level* L, int mode)
 {
-    int zc;
-    dim3 g, b;
     mode = base_mode(mode);
-    if (bad_level(L) || !valid_stencil(S) || !tb2_plan(S, L, &zc, &g, &b, nullptr, mode)) return 0;
-    return (int64_t)g.x * g.y;
+    if (bad_level(L) || !valid_stencil(S)) return 0;
+    const PairPlan plan = tb2_plan(S, L, mode);
+    return plan.fills ? (int64_t)plan.grid.x * plan.grid.y : 0;
 }
 
 int gs_jacobi_sweep2_norm(const gs_stencil* S, const gs_level* L, int mode, double omega, double gamma,
@@ -112,84 +177,42 @@ int gs_jacobi_sweep2_norm_w(const gs_stencil* S, const gs_level* L, int mode, co
                             const double* v_in, double* v_out, const double* f, const double* w, int zlo, int zhi,
                             double* partials, hipStream_t st)
 {
-    int zc;
-    dim3 g, b;
-    bool y2 = false, xh = false;
     // GS_NEWTON_G: the GS_NEWTON_B kernels take gamma for the factor instead of loading it (Coef::bconst)
     const int bconst = mode == GS_NEWTON_G;
     mode = base_mode(mode);
     if (!S || !omegas || bad_level(L) || !valid_stencil(S) || !v_out || !f || v_in == v_out ||
         (!v_in && mode == GS_NONLINEAR) ||
-        (newtonish(mode) && !w) || mode < GS_LINEAR || mode > GS_NEWTON_B ||
-        !tb2_plan(S, L, &zc, &g, &b, &y2, mode, &xh))
+        (newtonish(mode) && !w) || mode < GS_LINEAR || mode > GS_NEWTON_B)
         return GS_EINVAL;
+    PairPlan plan = tb2_plan(S, L, mode);
+    if (!plan.fills) return GS_EINVAL;
     const Coef k = make_coef_w(S, L, omegas, 2, gamma, bconst);
-    const int nx = (int)L->nx, ny = (int)L->ny, nz = (int)L->nz;
+    const int nx = (int)L->nx;
+    const bool zv = !v_in, xh = plan.colb, y2 = !plan.colb;
+    // FX (r06): LINEAR plain pairs over rows of whole 128-point waves (512-point column blocks) take the instance
+    // without per-lane range selects (k_tb2y FX; GS_PAIR_FX=0: the general instance, A/B); so does GS_NEWTON_B's
+    // whole-row pair
+    const bool fx = (mode == GS_LINEAR && !zv && k.unit && kKnobs.pairFx &&
+                     ((xh && nx % (2 * WAVE * TBY_WX) == 0) || (y2 && nx % (2 * WAVE) == 0))) ||
+                    (mode == GS_NEWTON_B && !zv && y2 && k.unit && kKnobs.pairFx && nx % (2 * WAVE) == 0);
+    const PairKernel fn = tb2y_kernel(mode, zv, xh, k.unit, fx, false, false);
     // LINEAR zero-iterate pairs (the first sweep of a coarse level, v = 0: the lightest variant, three
     // blocks per CU) below 2^26 points: chunks fitted to whole rounds of resident blocks (256^3: 61 vs
     // 71 us; the same rule measured no better for the other pairs, worse for k_rr2 and for NEWTON's
     // zero-iterate pair at two blocks per CU: 133 vs 120 us, r02 tools/fit_session.sh)
     const bool refit = !v_in && !partials && (int64_t)L->nx * L->ny * L->nz < ((int64_t)1 << 26);
-#define GS_TBY2(M, Z, U, P) do { \
-        if (refit && M == GS_LINEAR) refit_chunks(&k_tb2y<M, newtonish(M) ? TBY_RY_NEWTON : TBY_RY, TBY_WX, true, false, Z, true, 0, P, false, U>, (int)(b.x * b.y * b.z), nz, 4, 64, true, 2.0, &zc, &g); \
-        hipLaunchKernelGGL((k_tb2y<M, newtonish(M) ? TBY_RY_NEWTON : TBY_RY, TBY_WX, true, false, Z, true, 0, P, false, U>), g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0, zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr); } while (0)
-#define GS_TBY1(M, Z, U) GS_TBY2(M, Z, U, tby_pfd(M))
-#define GS_TBY(M, Z) do { if (k.unit) GS_TBY1(M, Z, true); else GS_TBY1(M, Z, false); } while (0)
-#define GS_TBX1(M, Z, P, U) hipLaunchKernelGGL((k_tb2y<M, TBY_RY, TBY_WX, true, false, Z, true, 0, P, true, U>), g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0, zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr)
-#define GS_TBX(M, Z, P) do { if (k.unit) GS_TBX1(M, Z, P, true); else GS_TBX1(M, Z, P, false); } while (0)
-    const bool zv = !v_in;
-    // FX (r06): LINEAR plain pairs over rows of whole 128-point waves (512-point column blocks) take the instance
-    // without per-lane range selects (k_tb2y FX; GS_PAIR_FX=0: the general instance, A/B)
-    if (mode == GS_LINEAR && !zv && k.unit && kKnobs.pairFx &&
-        ((xh && nx % (2 * WAVE * TBY_WX) == 0) || (y2 && nx % (2 * WAVE) == 0))) {
-        if (xh)
-            hipLaunchKernelGGL((k_tb2y<GS_LINEAR, TBY_RY, TBY_WX, true, false, false, true, 0, 2, true, true, false, 0, true>),
-                               g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0,
-                               zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr);
-        else
-            hipLaunchKernelGGL((k_tb2y<GS_LINEAR, TBY_RY, TBY_WX, true, false, false, true, 0, 2, false, true, false, 0, true>),
-                               g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0,
-                               zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr);
-    } else if (mode == GS_NEWTON_B && !zv && y2 && k.unit && kKnobs.pairFx && nx % (2 * WAVE) == 0) {
-        hipLaunchKernelGGL((k_tb2y<GS_NEWTON_B, TBY_RY_NEWTON, TBY_WX, true, false, false, true, 0, 1, false, true, false, 0, true>),
-                           g, b, 0, st, k, v_in, f, w, v_out, partials, nx, ny, nz, L->ldy, L->ldz, zc, zlo ? 1 : 0,
-                           zhi ? 1 : 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr);
-    } else if (xh) {
-        if (mode == GS_LINEAR) {
-            if (zv) GS_TBX(GS_LINEAR, true, 1);
-            else GS_TBX(GS_LINEAR, false, 2);
-        } else if (mode == GS_NONLINEAR) GS_TBX(GS_NONLINEAR, false, 1);
-        else if (mode == GS_NEWTON_B && zv) GS_TBX(GS_NEWTON_B, true, 1);
-        else if (mode == GS_NEWTON_B) GS_TBX(GS_NEWTON_B, false, 1);
-        else if (zv) GS_TBX(GS_NEWTON, true, 1);
-        else GS_TBX(GS_NEWTON, false, 1);
-    } else {
-        if (mode == GS_LINEAR) {
-            if (zv) GS_TBY(GS_LINEAR, true);
-            else GS_TBY(GS_LINEAR, false);
-        } else if (mode == GS_NONLINEAR) GS_TBY(GS_NONLINEAR, false);
-        else if (mode == GS_NEWTON_B && zv) GS_TBY(GS_NEWTON_B, true);
-        else if (mode == GS_NEWTON_B) GS_TBY(GS_NEWTON_B, false);
-        else if (zv) GS_TBY(GS_NEWTON, true);
-        else GS_TBY(GS_NEWTON, false);
-    }
-#undef GS_TBX
-#undef GS_TBX1
-#undef GS_TBY
-#undef GS_TBY1
-#undef GS_TBY2
-    return launch_status();
+    if (refit && mode == GS_LINEAR && y2)
+        refit_chunks(fn, (int)(plan.block.x * plan.block.y * plan.block.z), L->nz, 4, 64, true, 2.0, &plan.zc,
+                     &plan.grid);
+    return launch_tb2y(fn, plan, k, L, v_in, f, w, v_out, partials, zlo, zhi, st);
 }
 
 // The fused triple (k_tb3y): LINEAR, whole rows of <= 512 points, whole levels (z0 = 0), the pair's plan
 int gs_jacobi_sweep3_supported(const gs_stencil* S, const gs_level* L)
 {
-    int zc;
-    dim3 g, b;
-    bool y2 = false, xh = false;
     if (!S || bad_level(L) || !valid_stencil(S) || L->z0 != 0) return 0;
-    const int q = tb2_plan(S, L, &zc, &g, &b, &y2, GS_LINEAR, &xh);
-    return y2 ? q : 0;
+    const PairPlan plan = tb2_plan(S, L, GS_LINEAR);
+    return plan.colb ? 0 : plan.fills;
 }
 
 int gs_jacobi_sweep3(const gs_stencil* S, const gs_level* L, double omega, double gamma, const double* v_in,
@@ -202,56 +225,31 @@ int gs_jacobi_sweep3(const gs_stencil* S, const gs_level* L, double omega, doubl
 int gs_jacobi_sweep3_w(const gs_stencil* S, const gs_level* L, const double* omegas, double gamma, const double* v_in,
                        double* v_out, const double* f, hipStream_t st)
 {
-    int zc;
-    dim3 g, b;
-    bool y2 = false, xh = false;
-    if (!S || !omegas || bad_level(L) || !valid_stencil(S) || L->z0 != 0 || !v_in || !v_out || !f || v_in == v_out ||
-        !tb2_plan(S, L, &zc, &g, &b, &y2, GS_LINEAR, &xh) || !y2)
+    if (!S || !omegas || bad_level(L) || !valid_stencil(S) || L->z0 != 0 || !v_in || !v_out || !f || v_in == v_out)
         return GS_EINVAL;
+    const PairPlan plan = tb2_plan(S, L, GS_LINEAR);
+    if (!plan.fills || plan.colb) return GS_EINVAL;
     const Coef k = make_coef_w(S, L, omegas, 3, gamma);
     const int nx = (int)L->nx, ny = (int)L->ny, nz = (int)L->nz;
-#define GS_TB3(U, X, A)                                                                                                \
-    hipLaunchKernelGGL((k_tb3y<U, X, U, A>), g, b, 0, st, k, v_in, f, v_out, nx, ny, nz, L->ldy, L->ldz, zc)
-#define GS_TB3A(U, X)                                                                                                  \
-    do {                                                                                                               \
-        if (kKnobs.t3Saddr) GS_TB3(U, X, true);                                                                        \
-        else GS_TB3(U, X, false);                                                                                      \
-    } while (0)
     // FX: rows of whole 128-point waves, as the pair's (GS_PAIR_FX=0: the general instance). The unit-stencil instances
     // address through scalar row bases (GS_T3_SADDR=0: per-lane 64-bit addresses, A/B); the general-stencil instance
     // keeps the per-lane addresses, with scalar bases it spills 13 SGPRs to VGPR lanes
-    if (k.unit && kKnobs.pairFx && nx % (2 * WAVE) == 0) GS_TB3A(true, true);
-    else if (k.unit) GS_TB3A(true, false);
-    else GS_TB3(false, false, false);
-#undef GS_TB3A
-#undef GS_TB3
+    with_bools([&](auto U, auto X, auto A) {
+        if constexpr (U || (!X && !A))
+            hipLaunchKernelGGL((k_tb3y<U, X, U, A>), plan.grid, plan.block, 0, st, k, v_in, f, v_out, nx, ny, nz, L->ldy,
+                               L->ldz, plan.zc);
+    }, k.unit, k.unit && kKnobs.pairFx && nx % (2 * WAVE) == 0, k.unit && kKnobs.t3Saddr);
     return launch_status();
 }
 
 int gs_jacobi_sweep2_prolong_supported(const gs_stencil* S, const gs_level* L, int mode)
 {
-    int zc;
-    dim3 g, b;
-    bool y2 = false, xh = false;
-    mode = base_mode(mode);
-    // LINEAR and NEWTON (NONLINEAR carries restV too). Rows of more than 512 points (column blocks, XH,
-    // NEWTON too since r04) with the workspace of gs_jacobi_sweep2_prolong_ws_elems (the corrected edge
-    // columns). The fine planes' parities must be the global ones (even z0): they select each plane's
-    // combination
-    return !bad_level(L) && valid_stencil(S) && (mode == GS_LINEAR || newtonish(mode)) && L->z0 % 2 == 0 &&
-           tb2_plan(S, L, &zc, &g, &b, &y2, mode, &xh) && (y2 || xh);
+    return prolong_plan(S, L, base_mode(mode)).fills != 0;
 }
 
 int64_t gs_jacobi_sweep2_prolong_ws_elems(const gs_stencil* S, const gs_level* L, int mode)
 {
-    int zc;
-    dim3 g, b;
-    bool y2 = false, xh = false;
-    mode = base_mode(mode);
-    if (!gs_jacobi_sweep2_prolong_supported(S, L, mode) || !tb2_plan(S, L, &zc, &g, &b, &y2, mode, &xh) || !xh)
-        return 0;
-    const int64_t bw = 2 * WAVE * TBY_WX, nb = (L->nx + bw - 1) / bw - 1; // interior block boundaries
-    return nb * (L->nz + 4) * 4 * (L->ny + 2);
+    return prolong_ws_elems(L, prolong_plan(S, L, base_mode(mode)));
 }
 
 int gs_jacobi_sweep2_prolong(const gs_stencil* S, const gs_level* L, int mode, double omega, double gamma,
@@ -286,58 +284,41 @@ int gs_jacobi_sweep2_prolong_ws_w(const gs_stencil* S, const gs_level* L, int mo
                                   const gs_level* cl, double* v_out, const double* f, const double* w, int zlo, int zhi,
                                   double* ws, int64_t ws_elems, hipStream_t st)
 {
-    int zc;
-    dim3 g, b;
-    bool y2 = false, xh = false;
     const int bconst = mode == GS_NEWTON_G; // (Coef::bconst, as gs_jacobi_sweep2_norm)
     mode = base_mode(mode);
+    const PairPlan plan = prolong_plan(S, L, mode);
     // coarse plane of fine local plane z: (z >> 1) + czoff, z0 even (a slab, or a plane range of one)
-    const int64_t czoff = cl ? L->z0 / 2 - cl->z0 : 0;
-    if (!omegas || !gs_jacobi_sweep2_prolong_supported(S, L, mode) || bad_level(cl) || czoff < 0 || !v_in ||
+    const int64_t czoff = cl && plan.fills ? L->z0 / 2 - cl->z0 : 0;
+    if (!omegas || !plan.fills || bad_level(cl) || czoff < 0 || !v_in ||
         !coarse_v || !v_out || !f || v_in == v_out || (mode == GS_NONLINEAR) != (coarse_sub != nullptr) || (newtonish(mode) && !w) ||
-        (L->nx + 1) / 2 > cl->nx + 1 || (L->ny + 1) / 2 > cl->ny + 1 || (L->nz + 1) / 2 + czoff > cl->nz + 1 ||
-        !tb2_plan(S, L, &zc, &g, &b, &y2, mode, &xh))
+        (L->nx + 1) / 2 > cl->nx + 1 || (L->ny + 1) / 2 > cl->ny + 1 || (L->nz + 1) / 2 + czoff > cl->nz + 1)
         return GS_EINVAL;
-    const int64_t need = gs_jacobi_sweep2_prolong_ws_elems(S, L, mode);
+    const int64_t need = prolong_ws_elems(L, plan);
     if (need > 0 && (!ws || ws_elems < need)) return GS_EINVAL;
     // the kernel indexes the coarse field from the plane under fine local plane 0
     coarse_v += czoff * cl->ldz;
     if (coarse_sub) coarse_sub += czoff * cl->ldz;
     const Coef k = make_coef_w(S, L, omegas, 2, gamma, bconst);
+    const bool xh = plan.colb;
     if (xh && need > 0) {
         const int bw = 2 * WAVE * TBY_WX, nb = (int)((L->nx + bw - 1) / bw - 1);
         hipLaunchKernelGGL(k_pro_strip<false>, dim3((unsigned)((L->ny + 2 + 63) / 64), (unsigned)(L->nz + 4), (unsigned)nb),
                            dim3(256), 0, st, v_in, coarse_v, nullptr, ws, (int)L->nx, (int)L->ny, (int)L->nz, L->ldy,
                            L->ldz, cl->ldy, cl->ldz, bw, zlo ? 1 : 0, zhi ? 1 : 0);
     }
-#define GS_TBPF(M, P, U, X, WM, FXV) hipLaunchKernelGGL((k_tb2y<M, newtonish(M) ? TBY_RY_NEWTON : TBY_RY, WM, true, false, false, true, P, 1, X, U, false, 0, FXV>), g, b, 0, st, k, v_in, f, w, v_out, nullptr, (int)L->nx, (int)L->ny, (int)L->nz, L->ldy, L->ldz, zc, zlo ? 1 : 0, zhi ? 1 : 0, coarse_v, coarse_sub, (int)cl->nx, (int)cl->ny, (int)(cl->nz - czoff), cl->ldy, cl->ldz, ws)
-    // FX (r06, as the plain pairs): unit-stencil LINEAR / GS_NEWTON_B prolongation pairs of four x-waves over rows of
-    // whole 128-point waves (512-point column blocks) take the instance without per-lane range selects
-    const bool fx = k.unit && kKnobs.pairFx && b.y == TBY_WX && (xh ? L->nx % (2 * WAVE * TBY_WX) == 0 : L->nx % (2 * WAVE) == 0);
-#define GS_TBP1(M, P, U, X, WM) do { \
-        if constexpr (U && WM == TBY_WX && (M == GS_LINEAR || M == GS_NEWTON_B)) { \
-            if (fx) GS_TBPF(M, P, U, X, WM, true); \
-            else GS_TBPF(M, P, U, X, WM, false); \
-        } else { \
-            GS_TBPF(M, P, U, X, WM, false); \
-        } } while (0)
-#define GS_TBP(M, P, X, WM) do { if (k.unit) GS_TBP1(M, P, true, X, WM); else GS_TBP1(M, P, false, X, WM); } while (0)
+    const dim3 b = plan.block;
     // NEWTON's variant keeps ~37 KB of state per x-wave in LDS (its RECOMP rows): rows of <= 256 points
     // (two x-waves) take the instance sized for two, so that two blocks share a CU (8 waves, the VGPR
     // limit) instead of one block of 4 waves holding the whole LDS of a four-x-wave instance
     // (NEWTON column blocks: the RECOMP LDS state and the edge columns together, 144 B per lane spilled)
-    if (mode == GS_NEWTON_B && xh) GS_TBP(GS_NEWTON_B, 1, true, TBY_WX);
-    else if (mode == GS_NEWTON_B && b.y <= 2) GS_TBP(GS_NEWTON_B, 1, false, 2);
-    else if (mode == GS_NEWTON_B) GS_TBP(GS_NEWTON_B, 1, false, TBY_WX);
-    else if (mode == GS_NEWTON && xh) GS_TBP(GS_NEWTON, 1, true, TBY_WX);
-    else if (mode == GS_NEWTON && b.y <= 2) GS_TBP(GS_NEWTON, 1, false, 2);
-    else if (mode == GS_NEWTON) GS_TBP(GS_NEWTON, 1, false, TBY_WX);
-    else if (xh) GS_TBP(GS_LINEAR, 1, true, TBY_WX);
-    else GS_TBP(GS_LINEAR, 1, false, TBY_WX);
-#undef GS_TBP
-#undef GS_TBPF
-#undef GS_TBP1
-    return launch_status();
+    const bool wx2 = newtonish(mode) && !xh && b.y <= 2;
+    // FX (r06, as the plain pairs): unit-stencil LINEAR / GS_NEWTON_B prolongation pairs of four x-waves over rows of
+    // whole 128-point waves (512-point column blocks) take the instance without per-lane range selects
+    const bool fx = k.unit && kKnobs.pairFx && b.y == TBY_WX && (xh ? L->nx % (2 * WAVE * TBY_WX) == 0 : L->nx % (2 * WAVE) == 0);
+    const PairKernel fn = tb2y_kernel(mode, false, xh, k.unit, fx && !wx2 && (mode == GS_LINEAR || mode == GS_NEWTON_B), true, wx2);
+    return launch_tb2y(fn, plan, k, L, v_in, f, w, v_out, nullptr, zlo, zhi, st,
+                       PairOperands{coarse_v, coarse_sub, (int)cl->nx, (int)cl->ny, (int)(cl->nz - czoff), cl->ldy,
+                                    cl->ldz, ws});
 }
 
 // the small-level tiled kernels (gs_device.hpp k_tile_*): LINEAR / NEWTON, canonical stencil order, whole levels
@@ -367,15 +348,12 @@ int gs_smooth2_restrict_tiled_w(const gs_stencil* S, const gs_level* fl, int mod
         return GS_EINVAL;
     const Coef k = make_coef_w(S, fl, omegas, 2, gamma);
     const dim3 g((unsigned)((fl->nx + TS - 1) / TS), (unsigned)((fl->ny + TS - 1) / TS), (unsigned)((fl->nz + TS - 1) / TS));
-#define GS_TPR(M, Z, U) hipLaunchKernelGGL((k_tile_pre_rr<M, Z, U>), g, dim3(TS_T), 0, st, k, v_in, f, w, v_out, coarse_f, (int)fl->nx, (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz)
-#define GS_TPRM(M) do { \
-        if (!v_in) { if (k.unit) GS_TPR(M, true, true); else GS_TPR(M, true, false); } \
-        else { if (k.unit) GS_TPR(M, false, true); else GS_TPR(M, false, false); } } while (0)
-    if (mode == GS_NEWTON_B) GS_TPRM(GS_NEWTON_B);
-    else if (mode == GS_NEWTON) GS_TPRM(GS_NEWTON);
-    else GS_TPRM(GS_LINEAR);
-#undef GS_TPRM
-#undef GS_TPR
+    with_mode([&](auto M, auto Z, auto U) {
+        if constexpr (M != GS_NONLINEAR)
+            hipLaunchKernelGGL((k_tile_pre_rr<M, Z, U>), g, dim3(TS_T), 0, st, k, v_in, f, w, v_out, coarse_f, (int)fl->nx,
+                               (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy,
+                               cl->ldz);
+    }, mode, !v_in, k.unit);
     return launch_status();
 }
 
@@ -399,18 +377,11 @@ int gs_prolong_smooth2_tiled_w(const gs_stencil* S, const gs_level* fl, int mode
         return GS_EINVAL;
     const Coef k = make_coef_w(S, fl, omegas, 2, gamma);
     const dim3 g((unsigned)((fl->nx + TS - 1) / TS), (unsigned)((fl->ny + TS - 1) / TS), (unsigned)((fl->nz + TS - 1) / TS));
-#define GS_TP2(M, U) hipLaunchKernelGGL((k_tile_pro2<M, U>), g, dim3(TS_T), 0, st, k, v_in, coarse_v, f, w, v_out, (int)fl->nx, (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, cl->ldy, cl->ldz)
-    if (mode == GS_NEWTON_B) {
-        if (k.unit) GS_TP2(GS_NEWTON_B, true);
-        else GS_TP2(GS_NEWTON_B, false);
-    } else if (mode == GS_NEWTON) {
-        if (k.unit) GS_TP2(GS_NEWTON, true);
-        else GS_TP2(GS_NEWTON, false);
-    } else {
-        if (k.unit) GS_TP2(GS_LINEAR, true);
-        else GS_TP2(GS_LINEAR, false);
-    }
-#undef GS_TP2
+    with_mode([&](auto M, auto U) {
+        if constexpr (M != GS_NONLINEAR)
+            hipLaunchKernelGGL((k_tile_pro2<M, U>), g, dim3(TS_T), 0, st, k, v_in, coarse_v, f, w, v_out, (int)fl->nx,
+                               (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, cl->ldy, cl->ldz);
+    }, mode, k.unit);
     return launch_status();
 }
 
@@ -509,15 +480,12 @@ int gs_residual_restrict_slab(const gs_stencil* S, const gs_level* fl, int mode,
         const dim3 g((unsigned)rows, (unsigned)((cl->nz + zc - 1) / zc)), b(WAVE, (unsigned)wxs);
         // (the kernel's one operand slot and its non-temporal loads of the rows no neighbouring block reads: the
         // measured choices)
-#define GS_RR2U(M, N, U) hipLaunchKernelGGL((k_rr2<M, N, U>), g, b, 0, st, k, v, f, w, ca, cb, (int)fl->nx, (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz, (int)zc, zhi ? 1 : 0, kKnobs.rrReverse)
-#define GS_RR2(M, N) do { if (k.unit) GS_RR2U(M, N, true); else GS_RR2U(M, N, false); } while (0)
-        if (mode == GS_LINEAR && nr == 2) GS_RR2(GS_LINEAR, 2);
-        else if (mode == GS_LINEAR) GS_RR2(GS_LINEAR, 1);
-        else if (mode == GS_NONLINEAR) GS_RR2(GS_NONLINEAR, 1);
-        else if (mode == GS_NEWTON_B) GS_RR2(GS_NEWTON_B, 1);
-        else GS_RR2(GS_NEWTON, 1);
-#undef GS_RR2
-#undef GS_RR2U
+        with_mode([&](auto M, auto N2, auto U) {
+            if constexpr (!N2 || M == GS_LINEAR)
+                hipLaunchKernelGGL((k_rr2<M, N2 ? 2 : 1, U>), g, b, 0, st, k, v, f, w, ca, cb, (int)fl->nx, (int)fl->ny,
+                                   (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz,
+                                   (int)zc, zhi ? 1 : 0, kKnobs.rrReverse);
+        }, mode, nr == 2, k.unit);
         return launch_status();
     }
     StencilOffsets so;
@@ -530,12 +498,11 @@ int gs_residual_restrict_slab(const gs_stencil* S, const gs_level* fl, int mode,
     zc = zc < 1 ? 1 : (zc > 16 ? 16 : zc);
     const dim3 g((unsigned)((cl->nx + RR_TXC - 1) / RR_TXC), (unsigned)((cl->ny + RR_TYC - 1) / RR_TYC),
                  (unsigned)((cl->nz + zc - 1) / zc));
-#define GS_RR(M) hipLaunchKernelGGL(k_resrestrict<M>, g, dim3(RR_T), 0, st, k, so, v, f, w, ca, cb, (int)fl->nx, (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz, (int)zoff, (int)zc)
-    if (mode == GS_LINEAR) GS_RR(GS_LINEAR);
-    else if (mode == GS_NONLINEAR) GS_RR(GS_NONLINEAR);
-    else if (mode == GS_NEWTON_B) GS_RR(GS_NEWTON_B);
-    else GS_RR(GS_NEWTON);
-#undef GS_RR
+    with_mode([&](auto M) {
+        hipLaunchKernelGGL(k_resrestrict<M>, g, dim3(RR_T), 0, st, k, so, v, f, w, ca, cb, (int)fl->nx, (int)fl->ny,
+                           (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz,
+                           (int)zoff, (int)zc);
+    }, mode);
     return launch_status();
 }
 
@@ -564,12 +531,10 @@ int gs_prolong_add(const double* coarse_v, const double* coarse_sub, const gs_le
     if ((fl->nx + 1) / 2 > cl->nx + 1 || (fl->ny + 1) / 2 > cl->ny + 1 || clo < 0 || chi > cl->nz + 1)
         return GS_EINVAL;
     const dim3 g((unsigned)((fl->nx + 127) / 128), (unsigned)((fl->ny + 3) / 4), (unsigned)fl->nz), b(64, 4);
-    if (coarse_sub)
-        hipLaunchKernelGGL(k_prolong_add<true>, g, b, 0, st, coarse_v, coarse_sub, fine_v, (int)fl->nx, (int)fl->ny,
+    with_bools([&](auto SUB) {
+        hipLaunchKernelGGL(k_prolong_add<SUB>, g, b, 0, st, coarse_v, coarse_sub, fine_v, (int)fl->nx, (int)fl->ny,
                            (int)fl->nz, fl->ldy, fl->ldz, cl->ldy, cl->ldz, (int)fl->z0, (int)cl->z0);
-    else
-        hipLaunchKernelGGL(k_prolong_add<false>, g, b, 0, st, coarse_v, nullptr, fine_v, (int)fl->nx, (int)fl->ny,
-                           (int)fl->nz, fl->ldy, fl->ldz, cl->ldy, cl->ldz, (int)fl->z0, (int)cl->z0);
+    }, coarse_sub != nullptr);
     return launch_status();
 }
 
@@ -590,8 +555,8 @@ int gs_fmg_prolong(const double* coarse, const gs_level* cl, double* fine, const
     // rounds of resident blocks (fit_chunk; each chunk stages three planes more than it has cells)
     const int64_t cells = cl->nz + 1;
     const int64_t tiles = ((cl->nx + FP_TX) / FP_TX) * ((cl->ny + FP_TY) / FP_TY);
-    const void* fn = nt ? (const void*)k_fmg_prolong<true> : (const void*)k_fmg_prolong<false>;
-    int zc = fit_chunk(tiles, cells, resident_blocks(fn, FP_TX * FP_TY), 8, 64, false, 3.0);
+    const auto fn = nt ? k_fmg_prolong<true> : k_fmg_prolong<false>;
+    int zc = fit_chunk(tiles, cells, resident_blocks((const void*)fn, FP_TX * FP_TY), 8, 64, false, 3.0);
     if (zc < 8) zc = tiles >= 256 && cells >= 128 ? 32 : 8; // (GS_FIT_ROUNDS=0)
     const dim3 g((unsigned)((cl->nx + FP_TX) / FP_TX), (unsigned)((cl->ny + FP_TY) / FP_TY),
                  (unsigned)((cells + zc - 1) / zc)),
@@ -599,12 +564,8 @@ int gs_fmg_prolong(const double* coarse, const gs_level* cl, double* fine, const
     if (g.y > 65535u || g.z > 65535u) return GS_EINVAL;
     // the fine pair (2i+1, 2i+2) as one 16-byte store where the layout aligns it (gs_field_layout does)
     const int al = ((reinterpret_cast<uintptr_t>(fine + 1) & 15) == 0 && fl->ldy % 2 == 0 && fl->ldz % 2 == 0) ? 1 : 0;
-    if (nt)
-        hipLaunchKernelGGL(k_fmg_prolong<true>, g, b, 0, st, coarse, fine, (int)cl->nx, (int)cl->ny, (int)cl->nz,
-                           cl->ldy, cl->ldz, fl->ldy, fl->ldz, zc, al);
-    else
-        hipLaunchKernelGGL(k_fmg_prolong<false>, g, b, 0, st, coarse, fine, (int)cl->nx, (int)cl->ny, (int)cl->nz,
-                           cl->ldy, cl->ldz, fl->ldy, fl->ldz, zc, al);
+    hipLaunchKernelGGL(fn, g, b, 0, st, coarse, fine, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz, fl->ldy,
+                       fl->ldz, zc, al);
     return launch_status();
 }
 
@@ -639,16 +600,7 @@ int gs_newton_F_update(const gs_stencil* S, const gs_level* L, double gamma, con
 {
     if (!w || !e || !F || !w_out || !f || w_out == w || w_out == e || !gs_newton_F_update_supported(S, L))
         return GS_EINVAL;
-    const Coef k = make_coef(S, L, 0.0, gamma);
-    const PassPlan plan = pass_plan(S, L); // the grid and partial layout of gs_newton_F (k_rb KIND 1)
-    const dim3 b(WAVE, RB_W);
-    if (k.unit)
-        hipLaunchKernelGGL((k_newton_upd<RB_RY, RB_W, true>), plan.grid, b, 0, st, k, w, e, F, w_out, f, partials,
-                           (int)L->nx, (int)L->ny, (int)L->nz, L->ldy, L->ldz, plan.zc, nullptr, 0, 0, 0, 0, 0, nullptr);
-    else
-        hipLaunchKernelGGL((k_newton_upd<RB_RY, RB_W, false>), plan.grid, b, 0, st, k, w, e, F, w_out, f, partials,
-                           (int)L->nx, (int)L->ny, (int)L->nz, L->ldy, L->ldz, plan.zc, nullptr, 0, 0, 0, 0, 0, nullptr);
-    return launch_status();
+    return launch_newton_upd(S, L, gamma, w, e, F, w_out, f, partials, nullptr, nullptr, nullptr, st);
 }
 
 int gs_newton_F_update_restrict_supported(const gs_stencil* S, const gs_level* L, const gs_level* cl)
@@ -676,19 +628,7 @@ int gs_newton_F_update_restrict_bfac(const gs_stencil* S, const gs_level* L, dou
         !gs_newton_F_update_restrict_supported(S, L, cl))
         return GS_EINVAL;
     static_assert(RB_RY == 2, "the fused restriction takes two fine rows per wave");
-    const Coef k = make_coef(S, L, 0.0, gamma);
-    const PassPlan plan = pass_plan(S, L); // the same grid / partials as gs_newton_F_update
-    const dim3 b(WAVE, RB_W);
-#define GS_NUR(U, B) hipLaunchKernelGGL((k_newton_upd<RB_RY, RB_W, U, true, B>), plan.grid, b, 0, st, k, w, e, F, w_out, f, partials, (int)L->nx, (int)L->ny, (int)L->nz, L->ldy, L->ldz, plan.zc, coarse_w, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz, b_out)
-    if (b_out) {
-        if (k.unit) GS_NUR(true, true);
-        else GS_NUR(false, true);
-    } else {
-        if (k.unit) GS_NUR(true, false);
-        else GS_NUR(false, false);
-    }
-#undef GS_NUR
-    return launch_status();
+    return launch_newton_upd(S, L, gamma, w, e, F, w_out, f, partials, coarse_w, cl, b_out, st);
 }
 
 int gs_newton_bfac(const gs_level* L, double gamma, const double* w, double* b, hipStream_t st)
@@ -784,10 +724,7 @@ static int coarse_cycle(const gs_stencil* S, const gs_coarse_level* lv, int n, i
         L.vz = a.v_zero != 0;
         L.k = make_coef(S, g, omega, gamma);
     }
-    if (mode == GS_LINEAR) hipLaunchKernelGGL(k_coarse_cycle<GS_LINEAR>, dim3(1), dim3(CC_T), 0, st, P);
-    else if (mode == GS_NONLINEAR) hipLaunchKernelGGL(k_coarse_cycle<GS_NONLINEAR>, dim3(1), dim3(CC_T), 0, st, P);
-    else if (mode == GS_NEWTON_B) hipLaunchKernelGGL(k_coarse_cycle<GS_NEWTON_B>, dim3(1), dim3(CC_T), 0, st, P);
-    else hipLaunchKernelGGL(k_coarse_cycle<GS_NEWTON>, dim3(1), dim3(CC_T), 0, st, P);
+    with_mode([&](auto M) { hipLaunchKernelGGL(k_coarse_cycle<M>, dim3(1), dim3(CC_T), 0, st, P); }, mode);
     return launch_status();
 }
 

@@ -118,8 +118,8 @@ int gs_fmg_prolong_pa(const double* coarse, const gs_level* cl, double* fine, co
     // grid whole rounds of resident blocks (fit_chunk; a chunk stages about three coarse planes, six fine ones, more
     // than it covers)
     const int64_t tiles = ((fl->nx + 2 * FQ_TX - 1) / (2 * FQ_TX)) * ((fl->ny + 2 * FQ_TY - 1) / (2 * FQ_TY));
-    const void* fn = nt ? (const void*)k_fmg_prolong_pa<true> : (const void*)k_fmg_prolong_pa<false>;
-    int zc = fit_chunk(tiles, fl->nz, resident_blocks(fn, FQ_T), 16, 128, true, 6.0);
+    const auto fn = nt ? k_fmg_prolong_pa<true> : k_fmg_prolong_pa<false>;
+    int zc = fit_chunk(tiles, fl->nz, resident_blocks((const void*)fn, FQ_T), 16, 128, true, 6.0);
     if (zc < 16) zc = tiles >= 256 && fl->nz >= 256 ? 64 : 16; // (GS_FIT_ROUNDS=0)
     const dim3 g((unsigned)((fl->nx + 2 * FQ_TX - 1) / (2 * FQ_TX)), (unsigned)((fl->ny + 2 * FQ_TY - 1) / (2 * FQ_TY)),
                  (unsigned)((fl->nz + zc - 1) / zc)),
@@ -132,12 +132,8 @@ int gs_fmg_prolong_pa(const double* coarse, const gs_level* cl, double* fine, co
     }
     // the fine pair (x odd, x + 1) as one 16-byte store where the layout aligns it (gs_field_layout does)
     const int al = ((reinterpret_cast<uintptr_t>(fine + 1) & 15) == 0 && fl->ldy % 2 == 0 && fl->ldz % 2 == 0) ? 1 : 0;
-    if (nt)
-        hipLaunchKernelGGL(k_fmg_prolong_pa<true>, g, b, 0, st, d, coarse, fine, (int)cl->nx, (int)cl->ny, (int)cl->nz,
-                           (int)fl->nx, (int)fl->ny, (int)fl->nz, cl->ldy, cl->ldz, fl->ldy, fl->ldz, zc, al);
-    else
-        hipLaunchKernelGGL(k_fmg_prolong_pa<false>, g, b, 0, st, d, coarse, fine, (int)cl->nx, (int)cl->ny, (int)cl->nz,
-                           (int)fl->nx, (int)fl->ny, (int)fl->nz, cl->ldy, cl->ldz, fl->ldy, fl->ldz, zc, al);
+    hipLaunchKernelGGL(fn, g, b, 0, st, d, coarse, fine, (int)cl->nx, (int)cl->ny, (int)cl->nz, (int)fl->nx, (int)fl->ny,
+                       (int)fl->nz, cl->ldy, cl->ldz, fl->ldy, fl->ldz, zc, al);
     return launch_status();
 }
 
@@ -156,14 +152,10 @@ int gs_prolong_add_pa(const double* coarse_v, const double* coarse_sub, const gs
 {
     if (!coarse_v || !fine_v || bad_transfer(fl, cl, T)) return GS_EINVAL;
     const dim3 g((unsigned)((fl->nx + 127) / 128), (unsigned)((fl->ny + 3) / 4), (unsigned)fl->nz), b(64, 4);
-    if (coarse_sub)
-        hipLaunchKernelGGL(k_prolong_add_pa<true>, g, b, 0, st, device_tables(T), coarse_v, coarse_sub, fine_v,
-                           (int)fl->nx, (int)fl->ny, (int)cl->nx, (int)cl->ny, (int)cl->nz, fl->ldy, fl->ldz, cl->ldy,
-                           cl->ldz);
-    else
-        hipLaunchKernelGGL(k_prolong_add_pa<false>, g, b, 0, st, device_tables(T), coarse_v, coarse_sub, fine_v,
-                           (int)fl->nx, (int)fl->ny, (int)cl->nx, (int)cl->ny, (int)cl->nz, fl->ldy, fl->ldz, cl->ldy,
-                           cl->ldz);
+    with_bools([&](auto SUB) {
+        hipLaunchKernelGGL(k_prolong_add_pa<SUB>, g, b, 0, st, device_tables(T), coarse_v, coarse_sub, fine_v, (int)fl->nx,
+                           (int)fl->ny, (int)cl->nx, (int)cl->ny, (int)cl->nz, fl->ldy, fl->ldz, cl->ldy, cl->ldz);
+    }, coarse_sub != nullptr);
     return launch_status();
 }
 
@@ -188,15 +180,11 @@ int gs_residual_restrict_pa(const gs_stencil* S, const gs_level* fl, int mode, d
     const dim3 g((unsigned)((cl->nx + PA_TXC - 1) / PA_TXC), (unsigned)((cl->ny + PA_TYC - 1) / PA_TYC),
                  (unsigned)((cl->nz + zc - 1) / zc)),
         b(PA_T);
-#define GS_PA(M)                                                                                                       \
-    hipLaunchKernelGGL((k_resrestrict_pa<M>), g, b, 0, st, k, so, device_tables(T), v, f, w, coarse_f, (int)fl->nx,   \
-                       (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy,     \
-                       cl->ldz, (int)zc)
-    if (mode == GS_LINEAR) GS_PA(GS_LINEAR);
-    else if (mode == GS_NONLINEAR) GS_PA(GS_NONLINEAR);
-    else if (mode == GS_NEWTON_B) GS_PA(GS_NEWTON_B);
-    else GS_PA(GS_NEWTON);
-#undef GS_PA
+    with_mode([&](auto M) {
+        hipLaunchKernelGGL(k_resrestrict_pa<M>, g, b, 0, st, k, so, device_tables(T), v, f, w, coarse_f, (int)fl->nx,
+                           (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy,
+                           cl->ldz, (int)zc);
+    }, mode);
     return launch_status();
 }
 
