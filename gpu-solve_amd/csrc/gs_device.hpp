@@ -20,9 +20,12 @@
 #include <cmath>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
+#include <cxxabi.h>
 #include <map>
 #include <mutex>
+#include <string>
 #include <type_traits>
 #include <utility>
 
@@ -2214,8 +2217,78 @@ __global__ __launch_bounds__(CC_T) void k_coarse_cycle(CcPlan P)
     }
 }
 
+// The launch record (gs_launch_dry_run / gs_launch_record and the transfer library's pair): every kernel launch of a
+// product library goes through launch(), which notes the host function it is about to launch in a thread-local ring
+// and, while the calling thread's dry-run flag is set, skips the launch and nothing else. launch_record_take resolves
+// the noted functions to kernel names (hipKernelNameRefByPtr, demangled, without `(anonymous namespace)::`, the return
+// type and the argument list: `k_rb<0, 0, false, ...>`), newline-separated, and clears the record.
+struct LaunchRecord {
+    static constexpr int CAP = 16; // a call enqueues at most two kernels; an unread record keeps the latest CAP
+    const void* fn[CAP];
+    int64_t n;
+    bool dry;
+};
+thread_local LaunchRecord tlLaunches{};
+
+template <class... P, class... A>
+inline void launch(void (*fn)(P...), dim3 grid, dim3 block, hipStream_t st, A&&... args)
+{
+    LaunchRecord& r = tlLaunches;
+    r.fn[r.n++ % LaunchRecord::CAP] = reinterpret_cast<const void*>(fn);
+    if (r.dry) return;
+    hipLaunchKernelGGL(fn, grid, block, 0, st, static_cast<P>(args)...);
+}
+
+// dry-run: the launchers' runtime calls that stand in for a kernel (a memset of one partial, gs_copy's memcpy) are
+// skipped as a launch is, and record nothing
+bool launch_dry() { return tlLaunches.dry; }
+
+int launch_dry_run(int on)
+{
+    const int was = tlLaunches.dry ? 1 : 0;
+    tlLaunches.dry = on != 0;
+    return was;
+}
+
+int64_t launch_record_take(char* buf, int64_t cap)
+{
+    LaunchRecord& r = tlLaunches;
+    const int64_t n = r.n < LaunchRecord::CAP ? r.n : LaunchRecord::CAP;
+    std::string out;
+    for (int64_t i = r.n - n; i < r.n; i++) {
+        const void* fn = r.fn[i % LaunchRecord::CAP];
+        const char* mangled = fn ? hipKernelNameRefByPtr(fn, nullptr) : nullptr;
+        std::string name = mangled ? mangled : "?";
+        int status = -1;
+        char* d = mangled ? abi::__cxa_demangle(mangled, nullptr, nullptr, &status) : nullptr;
+        if (d && status == 0) name = d;
+        free(d);
+        const std::string anon = "(anonymous namespace)::";
+        for (size_t p = name.find(anon); p != std::string::npos; p = name.find(anon)) name.erase(p, anon.size());
+        if (name.compare(0, 5, "void ") == 0) name.erase(0, 5);
+        // the argument list: from the first '(' outside the template arguments
+        int depth = 0;
+        for (size_t p = 0; p < name.size(); p++) {
+            if (name[p] == '<') depth++;
+            else if (name[p] == '>') depth--;
+            else if (name[p] == '(' && depth == 0) {
+                name.erase(p);
+                break;
+            }
+        }
+        out += name;
+        out += '\n';
+    }
+    (void)hipGetLastError(); // without a device hipKernelNameRefByPtr leaves hipErrorNoDevice behind: not the caller's
+    if (!buf || cap < (int64_t)out.size() + 1) return -1; // (the record is kept)
+    memcpy(buf, out.c_str(), out.size() + 1);
+    r.n = 0;
+    return n;
+}
+
 int launch_status()
 {
+    if (tlLaunches.dry) return 0; // nothing was enqueued, and no device may exist to ask
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
@@ -3431,7 +3504,7 @@ int launch_tb2y(PairKernel fn, const PairPlan& p, const Coef& k, const gs_level*
                 const double* w, double* v_out, double* partials, int zlo, int zhi, hipStream_t st,
                 const PairOperands& o = PairOperands{})
 {
-    hipLaunchKernelGGL(fn, p.grid, p.block, 0, st, k, v_in, f, w, v_out, partials, (int)L->nx, (int)L->ny, (int)L->nz,
+    launch(fn, p.grid, p.block, st, k, v_in, f, w, v_out, partials, (int)L->nx, (int)L->ny, (int)L->nz,
                        L->ldy, L->ldz, p.zc, zlo ? 1 : 0, zhi ? 1 : 0, o.pc, o.ps, o.cnx, o.cny, o.cnz, o.cldy, o.cldz,
                        o.es);
     return launch_status();
@@ -3492,14 +3565,14 @@ int launch_pass(const gs_stencil* S, const gs_level* L, int mode, double omega, 
         // operator) for NONLINEAR only, as checked above
         with_mode([&](auto M, auto Z, auto U) {
             if constexpr ((!Z || (KIND == 0 && !ADD && M != GS_NONLINEAR)) && (KIND != 2 || M == GS_NONLINEAR))
-                hipLaunchKernelGGL((k_rb<M, KIND, ADD, RB_RY, RB_W, true, RB_NT, false, false, Z, U>), g, b, 0, st, k, v,
+                launch((k_rb<M, KIND, ADD, RB_RY, RB_W, true, RB_NT, false, false, Z, U>), g, b, st, k, v,
                                    f, w, out, partials, nx, ny, nz, L->ldy, L->ldz, plan.zc);
         }, mode, !v, k.unit);
     } else {
         const dim3 g = plan.grid, b(GN_BX, GN_BY);
         with_mode([&](auto M) {
             if constexpr (KIND != 2 || M == GS_NONLINEAR)
-                hipLaunchKernelGGL((k_generic<M, KIND, ADD>), g, b, 0, st, k, v, f, w, out, partials, nx, ny, nz, L->ldy,
+                launch((k_generic<M, KIND, ADD>), g, b, st, k, v, f, w, out, partials, nx, ny, nz, L->ldy,
                                    L->ldz);
         }, mode);
     }

@@ -63,7 +63,7 @@ int launch_newton_upd(const gs_stencil* S, const gs_level* L, double gamma, cons
     const gs_level c = cl ? *cl : gs_level{};
     with_bools([&](auto U, auto RS, auto BF) {
         if constexpr (RS || !BF)
-            hipLaunchKernelGGL((k_newton_upd<RB_RY, RB_W, U, RS, BF>), plan.grid, dim3(WAVE, RB_W), 0, st, k, w, e, F,
+            launch((k_newton_upd<RB_RY, RB_W, U, RS, BF>), plan.grid, dim3(WAVE, RB_W), st, k, w, e, F,
                                w_out, f, partials, (int)L->nx, (int)L->ny, (int)L->nz, L->ldy, L->ldz, plan.zc, coarse_w,
                                (int)c.nx, (int)c.ny, (int)c.nz, c.ldy, c.ldz, b_out);
     }, k.unit, cl != nullptr, b_out != nullptr);
@@ -94,7 +94,7 @@ int gs_rhs_init(const gs_level* L, double* f, int mode, double h0, double gamma,
 {
     if (bad_level(L) || !f) return GS_EINVAL;
     const dim3 g((unsigned)((L->nx + 2 + 63) / 64), (unsigned)((L->ny + 2 + 3) / 4), (unsigned)(L->nz + 2)), b(64, 4);
-    hipLaunchKernelGGL(k_rhs, g, b, 0, st, f, mode, h0, gamma, (int)L->nx, (int)L->ny, (int)L->nz, L->z0, L->ldy,
+    launch(k_rhs, g, b, st, f, mode, h0, gamma, (int)L->nx, (int)L->ny, (int)L->nz, L->z0, L->ldy,
                        L->ldz);
     return launch_status();
 }
@@ -112,7 +112,7 @@ int gs_jacobi_sweep_norm(const gs_stencil* S, const gs_level* L, int mode, doubl
     mode = base_mode(mode);
     if (!v_out || !f || v_in == v_out || (newtonish(mode) && !w)) return GS_EINVAL;
     if (partials && L && (L->nx == 0 || L->ny == 0 || L->nz == 0))
-        return (int)hipMemsetAsync(partials, 0, sizeof(double), st);
+        return launch_dry() ? 0 : (int)hipMemsetAsync(partials, 0, sizeof(double), st);
     return launch_pass<0, false>(S, L, mode, omega, gamma, v_in, f, w, v_out, partials, st);
 }
 
@@ -236,7 +236,7 @@ int gs_jacobi_sweep3_w(const gs_stencil* S, const gs_level* L, const double* ome
     // keeps the per-lane addresses, with scalar bases it spills 13 SGPRs to VGPR lanes
     with_bools([&](auto U, auto X, auto A) {
         if constexpr (U || (!X && !A))
-            hipLaunchKernelGGL((k_tb3y<U, X, U, A>), plan.grid, plan.block, 0, st, k, v_in, f, v_out, nx, ny, nz, L->ldy,
+            launch((k_tb3y<U, X, U, A>), plan.grid, plan.block, st, k, v_in, f, v_out, nx, ny, nz, L->ldy,
                                L->ldz, plan.zc);
     }, k.unit, k.unit && kKnobs.pairFx && nx % (2 * WAVE) == 0, k.unit && kKnobs.t3Saddr);
     return launch_status();
@@ -302,8 +302,8 @@ int gs_jacobi_sweep2_prolong_ws_w(const gs_stencil* S, const gs_level* L, int mo
     const bool xh = plan.colb;
     if (xh && need > 0) {
         const int bw = 2 * WAVE * TBY_WX, nb = (int)((L->nx + bw - 1) / bw - 1);
-        hipLaunchKernelGGL(k_pro_strip<false>, dim3((unsigned)((L->ny + 2 + 63) / 64), (unsigned)(L->nz + 4), (unsigned)nb),
-                           dim3(256), 0, st, v_in, coarse_v, nullptr, ws, (int)L->nx, (int)L->ny, (int)L->nz, L->ldy,
+        launch(k_pro_strip<false>, dim3((unsigned)((L->ny + 2 + 63) / 64), (unsigned)(L->nz + 4), (unsigned)nb),
+                           dim3(256), st, v_in, coarse_v, nullptr, ws, (int)L->nx, (int)L->ny, (int)L->nz, L->ldy,
                            L->ldz, cl->ldy, cl->ldz, bw, zlo ? 1 : 0, zhi ? 1 : 0);
     }
     const dim3 b = plan.block;
@@ -350,7 +350,7 @@ int gs_smooth2_restrict_tiled_w(const gs_stencil* S, const gs_level* fl, int mod
     const dim3 g((unsigned)((fl->nx + TS - 1) / TS), (unsigned)((fl->ny + TS - 1) / TS), (unsigned)((fl->nz + TS - 1) / TS));
     with_mode([&](auto M, auto Z, auto U) {
         if constexpr (M != GS_NONLINEAR)
-            hipLaunchKernelGGL((k_tile_pre_rr<M, Z, U>), g, dim3(TS_T), 0, st, k, v_in, f, w, v_out, coarse_f, (int)fl->nx,
+            launch((k_tile_pre_rr<M, Z, U>), g, dim3(TS_T), st, k, v_in, f, w, v_out, coarse_f, (int)fl->nx,
                                (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy,
                                cl->ldz);
     }, mode, !v_in, k.unit);
@@ -379,7 +379,7 @@ int gs_prolong_smooth2_tiled_w(const gs_stencil* S, const gs_level* fl, int mode
     const dim3 g((unsigned)((fl->nx + TS - 1) / TS), (unsigned)((fl->ny + TS - 1) / TS), (unsigned)((fl->nz + TS - 1) / TS));
     with_mode([&](auto M, auto U) {
         if constexpr (M != GS_NONLINEAR)
-            hipLaunchKernelGGL((k_tile_pro2<M, U>), g, dim3(TS_T), 0, st, k, v_in, coarse_v, f, w, v_out, (int)fl->nx,
+            launch((k_tile_pro2<M, U>), g, dim3(TS_T), st, k, v_in, coarse_v, f, w, v_out, (int)fl->nx,
                                (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, cl->ldy, cl->ldz);
     }, mode, k.unit);
     return launch_status();
@@ -399,14 +399,14 @@ int gs_residual(const gs_stencil* S, const gs_level* L, int mode, double gamma, 
     mode = base_mode(mode);
     if (!f || (newtonish(mode) && !w)) return GS_EINVAL;
     if (partials && (L && (L->nx == 0 || L->ny == 0 || L->nz == 0)))
-        return (int)hipMemsetAsync(partials, 0, sizeof(double), st);
+        return launch_dry() ? 0 : (int)hipMemsetAsync(partials, 0, sizeof(double), st);
     return launch_pass<1, false>(S, L, mode, 0.0, gamma, v, f, w, r, partials, st);
 }
 
 int gs_sumsq_finish(const double* partials, int64_t n, double* out, int accumulate, hipStream_t st)
 {
     if (!partials || !out || n < 0) return GS_EINVAL;
-    hipLaunchKernelGGL(k_sumsq_finish, dim3(1), dim3(FIN_T), 0, st, partials, n, out, accumulate);
+    launch(k_sumsq_finish, dim3(1), dim3(FIN_T), st, partials, n, out, accumulate);
     return launch_status();
 }
 
@@ -419,7 +419,7 @@ int gs_restrict2(const double* fine, const gs_level* fl, double* ca, double* cb,
         2 * cl->nz + zoff + 1 > fl->nz + 1)
         return GS_EINVAL;
     const dim3 g((unsigned)((cl->nx + 63) / 64), (unsigned)((cl->ny + 3) / 4), (unsigned)cl->nz), b(64, 4);
-    hipLaunchKernelGGL(k_restrict, g, b, 0, st, fine, ca, cb, (int)cl->nx, (int)cl->ny, (int)cl->nz, fl->ldy, fl->ldz,
+    launch(k_restrict, g, b, st, fine, ca, cb, (int)cl->nx, (int)cl->ny, (int)cl->nz, fl->ldy, fl->ldz,
                        cl->ldy, cl->ldz, (int)zoff);
     return launch_status();
 }
@@ -482,7 +482,7 @@ int gs_residual_restrict_slab(const gs_stencil* S, const gs_level* fl, int mode,
         // measured choices)
         with_mode([&](auto M, auto N2, auto U) {
             if constexpr (!N2 || M == GS_LINEAR)
-                hipLaunchKernelGGL((k_rr2<M, N2 ? 2 : 1, U>), g, b, 0, st, k, v, f, w, ca, cb, (int)fl->nx, (int)fl->ny,
+                launch((k_rr2<M, N2 ? 2 : 1, U>), g, b, st, k, v, f, w, ca, cb, (int)fl->nx, (int)fl->ny,
                                    (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz,
                                    (int)zc, zhi ? 1 : 0, kKnobs.rrReverse);
         }, mode, nr == 2, k.unit);
@@ -499,7 +499,7 @@ int gs_residual_restrict_slab(const gs_stencil* S, const gs_level* fl, int mode,
     const dim3 g((unsigned)((cl->nx + RR_TXC - 1) / RR_TXC), (unsigned)((cl->ny + RR_TYC - 1) / RR_TYC),
                  (unsigned)((cl->nz + zc - 1) / zc));
     with_mode([&](auto M) {
-        hipLaunchKernelGGL(k_resrestrict<M>, g, dim3(RR_T), 0, st, k, so, v, f, w, ca, cb, (int)fl->nx, (int)fl->ny,
+        launch(k_resrestrict<M>, g, dim3(RR_T), st, k, so, v, f, w, ca, cb, (int)fl->nx, (int)fl->ny,
                            (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz,
                            (int)zoff, (int)zc);
     }, mode);
@@ -516,7 +516,7 @@ int gs_interpolate(const double* coarse, const gs_level* cl, double* e, const gs
     if (!coarse || !e || bad_level(fl) || bad_level(cl) || fl->z0 != 0 || cl->z0 != 0) return GS_EINVAL;
     if ((fl->nx + 1) / 2 > cl->nx + 1 || (fl->ny + 1) / 2 > cl->ny + 1 || (fl->nz + 1) / 2 > cl->nz + 1) return GS_EINVAL;
     const dim3 g((unsigned)((fl->nx + 2 + 63) / 64), (unsigned)((fl->ny + 2 + 3) / 4), (unsigned)(fl->nz + 2)), b(64, 4);
-    hipLaunchKernelGGL(k_interpolate, g, b, 0, st, coarse, e, (int)fl->nx + 2, (int)fl->ny + 2, (int)fl->nz + 2,
+    launch(k_interpolate, g, b, st, coarse, e, (int)fl->nx + 2, (int)fl->ny + 2, (int)fl->nz + 2,
                        fl->ldy, fl->ldz, cl->ldy, cl->ldz);
     return launch_status();
 }
@@ -532,7 +532,7 @@ int gs_prolong_add(const double* coarse_v, const double* coarse_sub, const gs_le
         return GS_EINVAL;
     const dim3 g((unsigned)((fl->nx + 127) / 128), (unsigned)((fl->ny + 3) / 4), (unsigned)fl->nz), b(64, 4);
     with_bools([&](auto SUB) {
-        hipLaunchKernelGGL(k_prolong_add<SUB>, g, b, 0, st, coarse_v, coarse_sub, fine_v, (int)fl->nx, (int)fl->ny,
+        launch(k_prolong_add<SUB>, g, b, st, coarse_v, coarse_sub, fine_v, (int)fl->nx, (int)fl->ny,
                            (int)fl->nz, fl->ldy, fl->ldz, cl->ldy, cl->ldz, (int)fl->z0, (int)cl->z0);
     }, coarse_sub != nullptr);
     return launch_status();
@@ -564,7 +564,7 @@ int gs_fmg_prolong(const double* coarse, const gs_level* cl, double* fine, const
     if (g.y > 65535u || g.z > 65535u) return GS_EINVAL;
     // the fine pair (2i+1, 2i+2) as one 16-byte store where the layout aligns it (gs_field_layout does)
     const int al = ((reinterpret_cast<uintptr_t>(fine + 1) & 15) == 0 && fl->ldy % 2 == 0 && fl->ldz % 2 == 0) ? 1 : 0;
-    hipLaunchKernelGGL(fn, g, b, 0, st, coarse, fine, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz, fl->ldy,
+    launch(fn, g, b, st, coarse, fine, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz, fl->ldy,
                        fl->ldz, zc, al);
     return launch_status();
 }
@@ -641,7 +641,7 @@ int gs_newton_bfac(const gs_level* L, double gamma, const double* w, double* b, 
     const uintptr_t a = reinterpret_cast<uintptr_t>(bs), c = reinterpret_cast<uintptr_t>(ws);
     if ((a & 7) || (c & 7)) return GS_EINVAL;
     const int head = ((a ^ c) & 15) ? -1 : (int)((a & 15) / 8); // -1: no common dwordx4 alignment
-    hipLaunchKernelGGL(k_bfac, dim3(1024), dim3(256), 0, st, bs, ws, n, gamma, head);
+    launch(k_bfac, dim3(1024), dim3(256), st, bs, ws, n, gamma, head);
     return launch_status();
 }
 
@@ -651,7 +651,7 @@ int gs_fill(double* dst, double value, int64_t n, hipStream_t st)
     if (n == 0) return 0;
     int64_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_fill, dim3((unsigned)blocks), dim3(256), 0, st, dst, value, n);
+    launch(k_fill, dim3((unsigned)blocks), dim3(256), st, dst, value, n);
     return launch_status();
 }
 
@@ -661,8 +661,8 @@ int gs_copy(double* dst, const double* src, int64_t n, hipStream_t st)
     if (n == 0 || dst == src) return 0;
     const uintptr_t a = reinterpret_cast<uintptr_t>(dst), b = reinterpret_cast<uintptr_t>(src);
     if (((a ^ b) & 15) || (a & 7)) // no common dwordx4 alignment
-        return (int)hipMemcpyAsync(dst, src, sizeof(double) * n, hipMemcpyDeviceToDevice, st);
-    hipLaunchKernelGGL(k_copy, dim3(1024), dim3(256), 0, st, dst, src, n, (a & 15) ? 1 : 0);
+        return launch_dry() ? 0 : (int)hipMemcpyAsync(dst, src, sizeof(double) * n, hipMemcpyDeviceToDevice, st);
+    launch(k_copy, dim3(1024), dim3(256), st, dst, src, n, (a & 15) ? 1 : 0);
     return launch_status();
 }
 
@@ -672,7 +672,7 @@ int gs_axpy(double* y, const double* x, double a, int64_t n, hipStream_t st)
     if (n == 0) return 0;
     int64_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_axpy, dim3((unsigned)blocks), dim3(256), 0, st, y, x, a, n);
+    launch(k_axpy, dim3((unsigned)blocks), dim3(256), st, y, x, a, n);
     return launch_status();
 }
 
@@ -724,7 +724,7 @@ static int coarse_cycle(const gs_stencil* S, const gs_coarse_level* lv, int n, i
         L.vz = a.v_zero != 0;
         L.k = make_coef(S, g, omega, gamma);
     }
-    with_mode([&](auto M) { hipLaunchKernelGGL(k_coarse_cycle<M>, dim3(1), dim3(CC_T), 0, st, P); }, mode);
+    with_mode([&](auto M) { launch(k_coarse_cycle<M>, dim3(1), dim3(CC_T), st, P); }, mode);
     return launch_status();
 }
 
@@ -768,6 +768,10 @@ const char* gs_build_info(void)
            "one-workgroup coarse cycle; full-multigrid start (GS_FMG=k, gs_grid_fmg): tricubic gs_fmg_prolong "
            "(k_fmg_prolong: z-march, coarse planes staged in LDS, 16-byte fine stores); fp-contract=off";
 }
+
+int gs_launch_dry_run(int on) { return launch_dry_run(on); }
+
+int64_t gs_launch_record(char* buf, int64_t cap) { return launch_record_take(buf, cap); }
 
 } // extern "C"
 

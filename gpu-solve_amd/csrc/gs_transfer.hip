@@ -132,7 +132,7 @@ int gs_fmg_prolong_pa(const double* coarse, const gs_level* cl, double* fine, co
     }
     // the fine pair (x odd, x + 1) as one 16-byte store where the layout aligns it (gs_field_layout does)
     const int al = ((reinterpret_cast<uintptr_t>(fine + 1) & 15) == 0 && fl->ldy % 2 == 0 && fl->ldz % 2 == 0) ? 1 : 0;
-    hipLaunchKernelGGL(fn, g, b, 0, st, d, coarse, fine, (int)cl->nx, (int)cl->ny, (int)cl->nz, (int)fl->nx, (int)fl->ny,
+    launch(fn, g, b, st, d, coarse, fine, (int)cl->nx, (int)cl->ny, (int)cl->nz, (int)fl->nx, (int)fl->ny,
                        (int)fl->nz, cl->ldy, cl->ldz, fl->ldy, fl->ldz, zc, al);
     return launch_status();
 }
@@ -142,7 +142,7 @@ int gs_restrict_pa(const double* fine, const gs_level* fl, double* coarse_a, dou
 {
     if (!fine || !coarse_a || bad_transfer(fl, cl, T)) return GS_EINVAL;
     const dim3 g((unsigned)((cl->nx + 63) / 64), (unsigned)((cl->ny + 3) / 4), (unsigned)cl->nz), b(64, 4);
-    hipLaunchKernelGGL(k_restrict_pa, g, b, 0, st, device_tables(T), fine, coarse_a, coarse_b, (int)cl->nx, (int)cl->ny,
+    launch(k_restrict_pa, g, b, st, device_tables(T), fine, coarse_a, coarse_b, (int)cl->nx, (int)cl->ny,
                        (int)fl->nx, (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, cl->ldy, cl->ldz);
     return launch_status();
 }
@@ -153,7 +153,7 @@ int gs_prolong_add_pa(const double* coarse_v, const double* coarse_sub, const gs
     if (!coarse_v || !fine_v || bad_transfer(fl, cl, T)) return GS_EINVAL;
     const dim3 g((unsigned)((fl->nx + 127) / 128), (unsigned)((fl->ny + 3) / 4), (unsigned)fl->nz), b(64, 4);
     with_bools([&](auto SUB) {
-        hipLaunchKernelGGL(k_prolong_add_pa<SUB>, g, b, 0, st, device_tables(T), coarse_v, coarse_sub, fine_v, (int)fl->nx,
+        launch(k_prolong_add_pa<SUB>, g, b, st, device_tables(T), coarse_v, coarse_sub, fine_v, (int)fl->nx,
                            (int)fl->ny, (int)cl->nx, (int)cl->ny, (int)cl->nz, fl->ldy, fl->ldz, cl->ldy, cl->ldz);
     }, coarse_sub != nullptr);
     return launch_status();
@@ -181,11 +181,15 @@ int gs_residual_restrict_pa(const gs_stencil* S, const gs_level* fl, int mode, d
                  (unsigned)((cl->nz + zc - 1) / zc)),
         b(PA_T);
     with_mode([&](auto M) {
-        hipLaunchKernelGGL(k_resrestrict_pa<M>, g, b, 0, st, k, so, device_tables(T), v, f, w, coarse_f, (int)fl->nx,
+        launch(k_resrestrict_pa<M>, g, b, st, k, so, device_tables(T), v, f, w, coarse_f, (int)fl->nx,
                            (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy,
                            cl->ldz, (int)zc);
     }, mode);
     return launch_status();
 }
+
+int gs_transfer_launch_dry_run(int on) { return launch_dry_run(on); }
+
+int64_t gs_transfer_launch_record(char* buf, int64_t cap) { return launch_record_take(buf, cap); }
 
 } // extern "C"

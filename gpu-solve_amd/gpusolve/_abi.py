@@ -161,6 +161,9 @@ KERNEL_API = {
                                     C.c_double, C.c_int, C.c_int, C.c_void_p]),
     "gs_strerror": (C.c_char_p, [C.c_int]),
     "gs_build_info": (C.c_char_p, []),
+    # the launch record (per thread): dry-run switch, and the kernel names enqueued since the last call
+    "gs_launch_dry_run": (C.c_int, [C.c_int]),
+    "gs_launch_record": (i64, [C.c_char_p, i64]),
 }
 
 # libgpusolve_transfer.so (include/gpusolve_transfer.h): the position-aware grid transfers
@@ -177,6 +180,8 @@ TRANSFER_API = {
     "gs_fmg_axis": (C.c_int, [i64, i64, C.POINTER(C.c_int32), dptr]),
     "gs_fmg_prolong_pa": (C.c_int, [C.c_void_p, C.POINTER(gs_level), C.c_void_p, C.POINTER(gs_level),
                                     C.POINTER(gs_fmg_tables), C.c_void_p]),
+    "gs_transfer_launch_dry_run": (C.c_int, [C.c_int]),
+    "gs_transfer_launch_record": (i64, [C.c_char_p, i64]),
 }
 
 DRIVER_API = {

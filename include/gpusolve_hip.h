@@ -379,6 +379,20 @@ const char* gs_strerror(int code);
 /* Library build tag (kernel variant names), for logs. */
 const char* gs_build_info(void);
 
+/* The launch record: which kernel instance each launcher enqueued, for the tests that hold the instance table
+ * (tests/instance_table.py) to the library. Both are per calling thread and touch no device.
+ * gs_launch_dry_run(on): while on != 0 this thread's launchers do everything but enqueue their kernels: arguments are
+ * checked and plans made as usual, no pointer argument is dereferenced. The runtime calls that stand in for a kernel
+ * (the memset of the one partial of an empty level in gs_jacobi_sweep_norm / gs_residual, gs_copy's memcpy for
+ * operands without a common 16-byte phase) are skipped too and, as ever, record no name. Returns the previous setting.
+ * gs_launch_record(buf, cap): the names of the kernels this thread's launchers enqueued (or, in dry-run, would have)
+ * since the last successful call, oldest first, one per line ("k_rb<0, 0, false, 2, 4, true, true, false, false,
+ * false, true>": demangled, without namespace, return type and argument list), NUL-terminated; at most the latest 16.
+ * Returns their number and clears the record, or -1 with the record kept if buf is NULL or cap is too small. Either
+ * way the call resets the calling thread's HIP last-error (resolving a name without a device leaves one behind). */
+int gs_launch_dry_run(int on);
+int64_t gs_launch_record(char* buf, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,11 @@ int gs_fmg_axis(int64_t nf, int64_t nc, int32_t* cj, double* cw);
 int gs_fmg_prolong_pa(const double* coarse, const gs_level* cl, double* fine, const gs_level* fl,
                       const gs_fmg_tables* T, hipStream_t stream);
 
+/* This library's launch record: gs_launch_dry_run / gs_launch_record of include/gpusolve_hip.h for the launchers
+ * above (each library keeps its own record and its own dry-run flag). */
+int gs_transfer_launch_dry_run(int on);
+int64_t gs_transfer_launch_record(char* buf, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

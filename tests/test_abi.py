@@ -76,6 +76,11 @@ def test_python_binding_covers_headers():
     assert names == set(gsv._abi.DIAG_API), names ^ set(gsv._abi.DIAG_API)
     names = set(declared(os.path.join(REPO, "include", "gpusolve_driver.h")))
     assert names == set(gsv._abi.DRIVER_API), names ^ set(gsv._abi.DRIVER_API)
+    names = set(declared(os.path.join(REPO, "include", "gpusolve_transfer.h")))
+    assert names == set(gsv._abi.TRANSFER_API), names ^ set(gsv._abi.TRANSFER_API)
+    assert names <= exported(gsv._abi.TRANSFER_LIB)
+    assert {"gs_launch_dry_run", "gs_launch_record"} <= set(gsv._abi.KERNEL_API)
+    assert {"gs_transfer_launch_dry_run", "gs_transfer_launch_record"} <= names
 
 
 def test_libraries_load_without_gpu():

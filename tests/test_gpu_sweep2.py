@@ -78,9 +78,9 @@ def test_sweep2_equals_two_sweeps(shape, mode):
 
 @pytest.mark.parametrize("nx", [128, 512])
 def test_sweep2_extreme_magnitudes(nx):
-    """Whole-row LINEAR pairs test the fast h^2 division's range with floating-point compares (r06, div_hh_n FPC), the
-    single sweep with the exponent field: fields whose stencil sums straddle both ends of that range (2^-899, 2^601),
-    zeros, denormals and overflow must come out the same — bit for bit, NaNs as NaNs."""
+    """The whole-row LINEAR pairs (the FX / VEDGE instances) divide by h^2 in batches (div_hh_n), the single sweep
+    point by point: on fields whose stencil sums straddle both ends of the fast division's range (2^-899, 2^601), with
+    zeros, denormals and overflow, the pair must equal two single sweeps — bit for bit, NaNs as NaNs."""
     rng = np.random.default_rng(nx)
     shape = (nx, 6, 7)
     mags = np.array([0.0, 5e-324, 1e-310, 1e-280, 1e-272, 1.3e-271, 1e-270, 1e-200, 1.0, 1e100, 1e180, 4e180, 5e180,
