@@ -181,6 +181,49 @@ int gs_grid_fmg(void* grid, int cycles_per_level, double* residual)
     });
 }
 
+int gs_grid_pcg(void* grid, int print, double* hist, int cap, int* count)
+{
+    bool breakdown = false;
+    const int rc = guarded([&] {
+        auto& g = G(grid);
+        gs::HipSolver::pcgCheck(g); // a refused grid: before anything is touched
+        std::vector<double> h;
+        const bool was = g.printProgress;
+        g.printProgress = print != 0;
+        gs::HipSolver::history = &h;
+        try {
+            breakdown = gs::HipSolver::pcg(g);
+        } catch (...) {
+            gs::HipSolver::history = nullptr;
+            g.printProgress = was;
+            throw;
+        }
+        gs::HipSolver::history = nullptr;
+        g.printProgress = true;
+        if (count) *count = (int)h.size();
+        if (hist)
+            for (int i = 0; i < cap && i < (int)h.size(); i++) hist[i] = h[i];
+    });
+    return rc ? rc : (breakdown ? (int)GS_PCG_BREAKDOWN : 0);
+}
+
+int gs_grid_pcg_supported(void* grid)
+{
+    return guarded([&] { gs::HipSolver::pcgCheck(G(grid)); }) == 0 ? 1 : 0;
+}
+
+int gs_grid_pcg_record(void* grid, double* rec, int cap_iters)
+{
+    auto& st = G(grid).pcg;
+    if (st.started < 0 || !st.slots) {
+        g_err = "PCG: no run to report (gs_grid_pcg has not run on this grid)";
+        return -1;
+    }
+    for (int k = 0; rec && k < st.started && k < cap_iters; k++)
+        for (int i = 0; i < 6; i++) rec[6 * k + i] = st.slots[8 * k + i];
+    return st.started;
+}
+
 int gs_grid_fmg_start_level(void* grid) { return (int)gs::HipSolver::fmgStartLevel(G(grid)); }
 
 int gs_grid_set_weights(void* grid, const double* pre, int npre, const double* post, int npost)

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gpusolve_driver.h"
+#include "gpusolve_krylov.h"
 
 namespace gs {
 
@@ -202,6 +203,13 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
         sw.sweep3 = !on("GS_NO_SWEEP3");
         if (const char* e = std::getenv("GS_SWEEP3_MIN_POINTS")) sw.sweep3MinPoints = std::strtoll(e, nullptr, 10);
         if (const char* e = std::getenv("GS_FMG")) sw.fmg = std::max(0, std::atoi(e));
+        // GS_SOLVER=pcg|vcycle: what HipSolver::solve runs on a LINEAR grid; anything else throws here
+        if (const char* e = std::getenv("GS_SOLVER")) {
+            const std::string t = e;
+            if (t == "pcg") sw.solver = 1;
+            else if (t != "vcycle")
+                throw Error("GS_SOLVER=" + t + ": the value must be pcg or vcycle");
+        }
         // GS_OMEGAS: per-sweep relaxation weights; a malformed value or a count mismatch throws here, before any work
         if (const char* e = std::getenv("GS_OMEGAS")) weights = parseOmegas(e, preSmoothing, postSmoothing);
     }
@@ -489,6 +497,10 @@ HipGridData::~HipGridData()
     for (auto e : evBnd_)
         if (e) (void)hipEventDestroy(e);
     if (evNorm_) (void)hipEventDestroy(evNorm_);
+    if (pcg.rec) (void)hipFree(pcg.rec);
+    if (pcg.parts) (void)hipFree(pcg.parts);
+    if (pcg.slots) (void)hipHostFree(pcg.slots);
+    if (pcg.ev) (void)hipEventDestroy(pcg.ev);
 }
 
 void HipGridData::rec(const char* op, std::initializer_list<std::pair<const char*, long long>> kv, const char* field)
@@ -914,7 +926,24 @@ void HipSolver::solve(HipGridData& grid)
 {
     const bool print = grid.printProgress && grid.rank() == 0;
     const bool spec = speculationEnabled(grid);
+    if (grid.sw.solver == 1 && grid.mode == GridParams::LINEAR) pcgCheck(grid); // GS_SOLVER=pcg: likewise
     if (grid.sw.fmg > 0) fmgCheck(grid, grid.sw.fmg); // GS_FMG on a grid FMG cannot run on: before any work
+    if (grid.sw.solver == 1 && grid.mode == GridParams::LINEAR) {
+        // GS_SOLVER=pcg: the same lines and history from conjugate gradients; after GS_FMG=k from FMG's iterate, whose
+        // residual is PCG's first norm and has FMG's line
+        if (grid.sw.fmg > 0) {
+            const double initial = compResidual(grid, 0, false, true);
+            if (history) history->push_back(initial);
+            if (print) std::cout << "Inital residual: " << initial << '\n';
+            if (print) Timer::start();
+            fmgRun(grid, grid.sw.fmg);
+            grid.clock.segLevel.clear();
+            pcg(grid, &initial);
+        } else {
+            pcg(grid);
+        }
+        return;
+    }
     int pending = 0;
     const double initialResidual = spec ? speculativeSweep(grid, &pending) : compResidual(grid, 0, false, true);
     if (history) history->push_back(initialResidual);
@@ -1532,6 +1561,213 @@ double HipSolver::fmg(HipGridData& grid, int cyclesPerLevel)
 {
     fmgRun(grid, cyclesPerLevel);
     return compResidual(grid, 0, false, true);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Conjugate gradients preconditioned by the V-cycle.
+
+void HipGridData::pcgAlloc()
+{
+    const std::size_t need = maxiter + 1;
+    const gs_level& g0 = levels_[0].geom;
+    const char* const what = "PCG: allocating its level-0 fields and scalar record failed";
+    double *slots = nullptr, *slotsDev = nullptr;
+    if (pcg.slotCap < need) {
+        if (hipHostMalloc((void**)&slots, sizeof(double) * GS_PCG_REC * need, hipHostMallocMapped | hipHostMallocCoherent) !=
+                hipSuccess ||
+            hipHostGetDevicePointer((void**)&slotsDev, slots, 0) != hipSuccess) {
+            if (slots) (void)hipHostFree(slots);
+            (void)hipGetLastError();
+            throw Error(what);
+        }
+    }
+    if (!pcg.rec) {
+        double *rec = nullptr, *parts = nullptr;
+        hipEvent_t ev = nullptr;
+        try {
+            DeviceField r(g0.nx, g0.ny, g0.nz, stream_.s), z(g0.nx, g0.ny, g0.nz, stream_.s),
+                p0(g0.nx, g0.ny, g0.nz, stream_.s), p1(g0.nx, g0.ny, g0.nz, stream_.s);
+            const int64_t np = std::max<int64_t>(
+                1, std::max(gs_pcg_dir_num_partials(&stencilAbi, &g0),
+                            std::max(gs_pcg_step_num_partials(&g0), gs_dot_num_partials(&g0))));
+            if (hipMalloc((void**)&rec, sizeof(double) * GS_PCG_REC) != hipSuccess ||
+                hipMalloc((void**)&parts, sizeof(double) * np) != hipSuccess ||
+                hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
+                throw Error(what);
+            pcg.r = std::move(r);
+            pcg.z = std::move(z);
+            pcg.p[0] = std::move(p0);
+            pcg.p[1] = std::move(p1);
+        } catch (const Error&) {
+            if (rec) (void)hipFree(rec);
+            if (parts) (void)hipFree(parts);
+            if (ev) (void)hipEventDestroy(ev);
+            if (slots) (void)hipHostFree(slots);
+            (void)hipGetLastError(); // (the failed allocation's sticky error)
+            throw Error(what);
+        }
+        pcg.rec = rec;
+        pcg.parts = parts;
+        pcg.ev = ev;
+    }
+    if (slots) {
+        if (pcg.slots) {
+            check((int)hipStreamSynchronize(stream_.s), "hipStreamSynchronize"); // (no kernel still writes the old one)
+            (void)hipHostFree(pcg.slots);
+        }
+        pcg.slots = slots;
+        pcg.slotsDev = slotsDev;
+        pcg.slotCap = need;
+        pcg.started = -1;
+    }
+}
+
+// The cycle is a symmetric positive definite preconditioner only under these conditions (tests/test_pcg_cpu.py
+// measures the symmetry defect of the model cycle: 1e-15 where they hold, 4.3e-3 with pre = 2, post = 1)
+void HipSolver::pcgCheck(const HipGridData& grid)
+{
+    if (grid.mode != GridParams::LINEAR)
+        throw Error("PCG: LINEAR grids only (NONLINEAR and NEWTON are not linear systems)");
+    if (grid.nranks() > 1 || grid.trace)
+        throw Error("PCG: single-GPU grids only (not a Z-slab / RCCL or schedule-trace grid)");
+    if (grid.preSmoothing != grid.postSmoothing || grid.preSmoothing == 0)
+        throw Error("PCG: the cycle must smooth symmetrically: pre = post >= 1 (pre = " +
+                    std::to_string(grid.preSmoothing) + ", post = " + std::to_string(grid.postSmoothing) + ")");
+    if (grid.weighted()) {
+        std::vector<double> a(grid.wPre(), grid.wPre() + grid.preSmoothing),
+            b(grid.wPost(), grid.wPost() + grid.postSmoothing);
+        std::sort(a.begin(), a.end());
+        std::sort(b.begin(), b.end());
+        if (a != b)
+            throw Error("PCG: the post-smoothing weights must be the pre-smoothing weights in some order (the cycle is "
+                        "not symmetric otherwise)");
+    }
+    double wgt[27] = {};
+    const gs_stencil& S = grid.stencilAbi;
+    for (int i = 0; i < 7; i++) wgt[(S.ox[i] + 1) + 3 * (S.oy[i] + 1) + 9 * (S.oz[i] + 1)] += S.s[i];
+    for (int o = 0; o < 27; o++)
+        if (!(wgt[o] == wgt[26 - o]))
+            throw Error("PCG: the stencil must be symmetric: the weight at every offset o must be the weight at -o");
+    if (grid.transferMode == 0)
+        for (std::size_t l = 0; l + 1 < grid.numLevels(); l++)
+            if (!grid.levelAligned(l)) {
+                const auto& d = grid.getLevel(0).levelDim;
+                throw Error("PCG: the coarse grids of " + std::to_string(d[0]) + " x " + std::to_string(d[1]) + " x " +
+                            std::to_string(d[2]) +
+                            " do not align and the reference transfers diverge there: "
+                            "gs_grid_set_transfer(GS_TRANSFER_POSITION) / GS_TRANSFER=position");
+            }
+}
+
+namespace {
+// level 0's f and v stand in for the residual and the preconditioned residual while the cycle runs; put back on
+// every exit
+struct PcgSwap {
+    HipGridData::LevelData& L;
+    HipGridData::PcgState& st;
+    const bool vz;
+    PcgSwap(HipGridData::LevelData& l, HipGridData::PcgState& s) : L(l), st(s), vz(l.vZero)
+    {
+        L.f.swap(st.r);
+        L.v.swap(st.z);
+    }
+    ~PcgSwap()
+    {
+        L.f.swap(st.r);
+        L.v.swap(st.z);
+        L.vZero = vz;
+    }
+};
+} // namespace
+
+bool HipSolver::pcg(HipGridData& grid, const double* fmgInitial)
+{
+    pcgCheck(grid);
+    grid.pcgAlloc();
+    auto& st = grid.pcg;
+    auto& L0 = grid.getLevel(0);
+    const hipStream_t s = grid.stream();
+    const gs_stencil* S = &grid.stencilAbi;
+    const gs_level* G = &L0.geom;
+    const bool print = grid.printProgress;
+    materialize(grid, 0);
+    st.started = 0;
+    st.breakdown = false;
+    // r = f - A x0 and its norm
+    check(gs_residual(S, G, GS_LINEAR, grid.gamma, L0.v.data(), L0.f.data(), nullptr, st.r.data(), grid.partials(), s),
+          "gs_residual");
+    const double res0 = finishNorm(grid, gs_residual_num_partials(S, G));
+    const double initialResidual = fmgInitial ? *fmgInitial : res0;
+    if (history) history->push_back(res0);
+    if (fmgInitial) {
+        if (print) {
+            std::cout << "fmg: cycles: " << grid.sw.fmg << " residual: " << res0 << ' ';
+            Timer::stop();
+            Timer::start();
+        }
+        if (res0 <= initialResidual / (1.0 / grid.tol)) return false;
+    } else {
+        if (print) std::cout << "Inital residual: " << res0 << '\n';
+        if (print) Timer::start();
+    }
+    // z = M^-1 r (one V-cycle from the zero iterate with r as right-hand side), r . z, and the scalars it decides
+    auto tail = [&](bool first) {
+        {
+            PcgSwap sw(L0, st);
+            if (grid.sw.zeroGuess) {
+                L0.vZero = true;
+            } else {
+                L0.v.zero(s);
+                L0.vZero = false;
+            }
+            vcycleFrom(grid, 0);
+            materialize(grid, 0);
+            grid.clock.segLevel.clear(); // (the per-level clock times the V-cycle loop only)
+        }
+        check(gs_dot(G, st.r.data(), st.z.data(), st.parts, s), "gs_dot");
+        check(gs_pcg_scalars(first ? GS_PCG_RZ_FIRST : GS_PCG_RZ, st.parts, gs_dot_num_partials(G), st.rec, nullptr, s),
+              "gs_pcg_scalars");
+    };
+    tail(true);
+    bool tailDone = true;
+    int cur = 0; // p[cur]: the direction this iteration writes; p[cur ^ 1]: the previous one
+    for (std::size_t k = 0; k < grid.maxiter; k++) {
+        if (!tailDone) tail(false);
+        double* q = L0.vAlt.data();
+        check(gs_pcg_dir(S, G, st.z.data(), k == 0 ? nullptr : st.p[cur ^ 1].data(), st.p[cur].data(), q,
+                         st.rec + GS_PCG_BETA_I, st.parts, s),
+              "gs_pcg_dir");
+        check(gs_pcg_scalars(GS_PCG_PQ, st.parts, gs_pcg_dir_num_partials(S, G), st.rec, nullptr, s), "gs_pcg_scalars");
+        check(gs_pcg_step(G, L0.v.data(), st.r.data(), st.p[cur].data(), q, st.rec + GS_PCG_ALPHA_I, st.parts, s),
+              "gs_pcg_step");
+        check(gs_pcg_scalars(GS_PCG_RR, st.parts, gs_pcg_step_num_partials(G), st.rec, st.slotsDev + GS_PCG_REC * k, s),
+              "gs_pcg_scalars");
+        check((int)hipEventRecord(st.ev, s), "hipEventRecord");
+        st.started = (int)k + 1;
+        // the next iteration's cycle, dot product and beta behind the norm the host waits for: they write z, the
+        // record and the coarse levels only, so stopping here leaves x and r this iteration's
+        const bool ahead = grid.sw.pipeline && k + 1 < grid.maxiter;
+        if (ahead) tail(false);
+        tailDone = ahead;
+        check((int)hipEventSynchronize(st.ev), "hipEventSynchronize");
+        const volatile double* slot = st.slots + GS_PCG_REC * k;
+        // a breakdown: alpha was 0, so this iteration changed nothing (GS_PCG_BAD_RR: r . r is not finite, the iterate
+        // overflowed; the slot's 0 is no norm and must not count as converged)
+        if (slot[GS_PCG_FLAG_I] != 0.0) {
+            st.breakdown = true;
+            break;
+        }
+        const double res = std::sqrt(slot[GS_PCG_RR_I]);
+        if (history) history->push_back(res);
+        if (print) {
+            std::cout << "iter: " << k << " residual: " << res << ' ';
+            Timer::stop();
+            Timer::start();
+        }
+        if (res <= initialResidual / (1.0 / grid.tol)) break;
+        cur ^= 1;
+    }
+    return st.breakdown;
 }
 
 double HipSolver::cycleUp0(HipGridData& grid, int* pending, bool wait)

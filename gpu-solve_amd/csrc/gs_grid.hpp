@@ -175,6 +175,9 @@ public:
         // (HipSolver::fmg) before its first V-cycle — with GS_OMEGAS (weights, below) the switches that change the
         // iterate
         int fmg = 0;
+        // GS_SOLVER=pcg|vcycle (default vcycle): HipSolver::solve on a LINEAR grid runs HipSolver::pcg — conjugate
+        // gradients preconditioned by the V-cycle — instead of the V-cycle loop (after GS_FMG: from FMG's iterate)
+        int solver = 0;
     } sw;
     // Per-sweep relaxation weights (gs_grid_set_weights, GS_OMEGAS): preSmoothing pre weights followed by
     // postSmoothing post weights; empty (the default): every sweep takes omega. On every level the k-th
@@ -218,6 +221,23 @@ public:
     // levels coarseFrom .. numLevels()-1 run as ONE gs_coarse_cycle launch in every V-cycle
     // (numLevels(): none); set from GS_COARSE_POINTS at construction
     std::size_t coarseFrom = 0;
+    // HipSolver::pcg's state, allocated by its first call (pcgAlloc: all of it or nothing): four
+    // level-0 fields beside the hierarchy's — the residual r, the preconditioned residual z, the direction and the
+    // previous direction (q = A p lives in level 0's vAlt, which is dead outside a cycle) —, the device-resident
+    // scalar record, its own partial sums and the mapped, coherent pinned history (one slot per iteration: the
+    // norm-word pattern of hNorm_), from which gs_grid_pcg_record reads the last run
+    struct PcgState {
+        DeviceField r, z, p[2];
+        double* rec = nullptr;      // device: GS_PCG_REC doubles
+        double* parts = nullptr;    // device: the three passes' partial sums
+        double* slots = nullptr;    // pinned host: GS_PCG_REC doubles per iteration
+        double* slotsDev = nullptr; // ... as the device sees it
+        std::size_t slotCap = 0;
+        int started = -1;           // iterations the last run started (-1: no run yet)
+        bool breakdown = false;     // ... and whether it ended in a breakdown
+        hipEvent_t ev = nullptr;
+    } pcg;
+    void pcgAlloc(); // throws, leaving the state as it was
     LevelClock clock; // per-level timing (GS_METRICS)
     std::vector<std::string>* trace = nullptr; // schedule-trace mode (see the constructor)
     void rec(const char* op, std::initializer_list<std::pair<const char*, long long>> kv, const char* field = nullptr);
@@ -339,6 +359,13 @@ public:
     // grid.fmgProlongMode POSITION: every size, from the coarsest level, non-aligned transitions prolonged by
     // gs_fmg_prolong_pa and restricted by gs_restrict_pa (the grid's transfers must be POSITION where one exists).
     static double fmg(HipGridData& grid, int cyclesPerLevel);
+    // Conjugate gradients preconditioned by one V-cycle (vcycleFrom(0) from a zero iterate on the residual) on a
+    // LINEAR single-GPU grid whose cycle is symmetric (pcgCheck throws otherwise, before any work): from level 0's
+    // v as it stands, at most maxiter iterations, solve's stopping rule, history and print lines. fmgInitial: the
+    // norm solve() took before its GS_FMG pass (the tolerance's reference; the first norm then has FMG's line).
+    // Returns whether the run ended in a breakdown (p.q or r.z not a positive finite number).
+    static bool pcg(HipGridData& grid, const double* fmgInitial = nullptr);
+    static void pcgCheck(const HipGridData& grid);
     // the deepest level such that every transition above it is gs_fmg_prolong_supported (POSITION prolongation: the
     // coarsest level); 0: FMG not applicable
     static std::size_t fmgStartLevel(const HipGridData& grid);

@@ -23,6 +23,7 @@ from . import _abi
 from ._abi import GS_LINEAR, GS_MAX_WEIGHTS, GS_NEWTON, GS_NEWTON_B, GS_NEWTON_G, GS_NONLINEAR, gs_level, gs_params, gs_stencil, kernels, driver, diag  # noqa: F401
 from ._abi import GS_TRANSFER_POSITION, GS_TRANSFER_REFERENCE, gs_transfer_tables, transfer  # noqa: F401
 from ._abi import GS_FMG_PROLONG_ALIGNED, GS_FMG_PROLONG_POSITION, gs_fmg_tables  # noqa: F401
+from ._abi import GS_PCG_BREAKDOWN, krylov  # noqa: F401
 
 CANONICAL_OFFSETS = [(0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)]
 
@@ -224,6 +225,26 @@ class HipGridData:
             raise IndexError(level)
         return bool(r)
 
+    def pcg_supported(self) -> bool:
+        """Whether HipSolver.pcg can run on this grid as it is configured now (LINEAR, one GPU, a symmetric stencil
+        and a symmetric cycle: pre = post >= 1, post weights a permutation of the pre weights, POSITION transfers
+        where a transition is not aligned). False leaves the reason in pcg_refusal."""
+        ok = driver().gs_grid_pcg_supported(self.handle) == 1
+        self.pcg_refusal = None if ok else driver().gs_last_error().decode()
+        return ok
+
+    def pcg_record(self):
+        """The last HipSolver.pcg run's scalars, one dict per iteration it started (a run that broke down includes the
+        iteration that did): rz = r.z and beta as that iteration's direction used them, pq = p.q, alpha = rz / pq,
+        rr = the new r.r, flag (0, or GS_PCG_BAD_PQ | GS_PCG_BAD_RZ | GS_PCG_BAD_RR)."""
+        n = driver().gs_grid_pcg_record(self.handle, None, 0)
+        if n < 0:
+            raise GpuSolveError(driver().gs_last_error().decode())
+        buf = (C.c_double * max(1, 6 * n))()
+        driver().gs_grid_pcg_record(self.handle, buf, n)
+        keys = ("rz", "pq", "alpha", "beta", "rr", "flag")
+        return [dict(zip(keys, buf[6 * k:6 * k + 6])) for k in range(n)]
+
     def field(self, level: int, name: str) -> np.ndarray:
         """Copy of a padded field as a dense array indexed [x][y][z] (the reference's axis order)."""
         g = self.getLevel(level).geom
@@ -301,6 +322,23 @@ class HipSolver:
         r = C.c_double()
         _check(driver().gs_grid_fmg(grid.handle, cycles_per_level, C.byref(r)))
         return r.value
+
+    @staticmethod
+    def pcg(grid: HipGridData, print_progress: bool = False) -> List[float]:
+        """Conjugate gradients preconditioned by one V-cycle, from level 0's iterate as it stands (an upload or a
+        preceding fmg is honoured), with the grid's maxiter and tol and solve's stopping rule; returns the residual
+        history [||f - A x0||, then one norm per iteration]. LINEAR single-GPU grids whose cycle is symmetric
+        (grid.pcg_supported()); GpuSolveError with nothing touched otherwise. A breakdown (p.q or r.z not a positive
+        finite number: a zero right-hand side, or convergence to the last bit) ends the run cleanly with the last
+        complete iteration's x; grid.pcg_breakdown says whether that happened."""
+        cap = int(grid.params.maxiter) + 2
+        hist = (C.c_double * cap)()
+        n = C.c_int(0)
+        rc = driver().gs_grid_pcg(grid.handle, 1 if print_progress else 0, hist, cap, C.byref(n))
+        if rc not in (0, GS_PCG_BREAKDOWN):
+            _check(rc)
+        grid.pcg_breakdown = rc == GS_PCG_BREAKDOWN
+        return list(hist[: min(n.value, cap)])
 
     @staticmethod
     def jacobi(grid: HipGridData, level: int, sweeps: int):

@@ -12,6 +12,7 @@ LIB_DIR = os.path.join(PKG_ROOT, "lib")
 BIN_DIR = os.path.join(PKG_ROOT, "bin")
 KERNEL_LIB = os.path.join(LIB_DIR, "libgpusolve_hip.so")
 TRANSFER_LIB = os.path.join(LIB_DIR, "libgpusolve_transfer.so")  # position-aware transfers (include/gpusolve_transfer.h)
+KRYLOV_LIB = os.path.join(LIB_DIR, "libgpusolve_krylov.so")  # the PCG passes (include/gpusolve_krylov.h)
 DIAG_LIB = os.path.join(LIB_DIR, "libgpusolve_diag.so")  # tools/ and tests/ only (include/gpusolve_diag.h)
 DRIVER_LIB = os.path.join(LIB_DIR, "libgpusolve_driver.so")
 EXECUTABLE = os.path.join(BIN_DIR, "GpuSolve-hip")
@@ -22,6 +23,11 @@ GS_NEWTON_G = 4  # GS_NEWTON_B whose factor field holds gamma everywhere (the fi
 GS_EINVAL = 100001
 GS_TRANSFER_REFERENCE, GS_TRANSFER_POSITION = 0, 1  # gs_grid_set_transfer (include/gpusolve_driver.h)
 GS_FMG_PROLONG_ALIGNED, GS_FMG_PROLONG_POSITION = 0, 1  # gs_grid_set_fmg_prolong (include/gpusolve_driver.h)
+# include/gpusolve_krylov.h: the record's layout, its flag bits, and what gs_pcg_scalars does
+GS_PCG_RZ_I, GS_PCG_PQ_I, GS_PCG_ALPHA_I, GS_PCG_BETA_I, GS_PCG_RR_I, GS_PCG_FLAG_I, GS_PCG_REC = 0, 1, 2, 3, 4, 5, 8
+GS_PCG_BAD_PQ, GS_PCG_BAD_RZ, GS_PCG_BAD_RR = 1, 2, 4
+GS_PCG_PQ, GS_PCG_RR, GS_PCG_RZ, GS_PCG_RZ_FIRST = 0, 1, 2, 3
+GS_PCG_BREAKDOWN = 2  # gs_grid_pcg's return code for a run that ended in a breakdown (include/gpusolve_driver.h)
 GS_MAX_WEIGHTS = 8  # per-sweep relaxation weights per smoothing leg (include/gpusolve_hip.h)
 
 dptr = C.POINTER(C.c_double)
@@ -184,6 +190,20 @@ TRANSFER_API = {
     "gs_transfer_launch_record": (i64, [C.c_char_p, i64]),
 }
 
+# libgpusolve_krylov.so (include/gpusolve_krylov.h): the level-0 passes of preconditioned conjugate gradients
+KRYLOV_API = {
+    "gs_pcg_dir": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gs_pcg_dir_num_partials": (i64, [C.POINTER(gs_stencil), C.POINTER(gs_level)]),
+    "gs_pcg_dir_kernel": (C.c_char_p, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int]),
+    "gs_pcg_step": (C.c_int, [C.POINTER(gs_level), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p]),
+    "gs_pcg_step_num_partials": (i64, [C.POINTER(gs_level)]),
+    "gs_dot": (C.c_int, [C.POINTER(gs_level), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gs_dot_num_partials": (i64, [C.POINTER(gs_level)]),
+    "gs_pcg_scalars": (C.c_int, [C.c_int, C.c_void_p, i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 DRIVER_API = {
     "gs_parse_config": (C.c_int, [C.c_char_p, C.POINTER(gs_params)]),
     "gs_grid_create": (C.c_void_p, [C.POINTER(gs_params)]),
@@ -193,6 +213,9 @@ DRIVER_API = {
     "gs_grid_vcycle_level": (C.c_int, [C.c_void_p, C.c_int]),
     "gs_grid_fmg": (C.c_int, [C.c_void_p, C.c_int, dptr]),
     "gs_grid_fmg_start_level": (C.c_int, [C.c_void_p]),
+    "gs_grid_pcg": (C.c_int, [C.c_void_p, C.c_int, dptr, C.c_int, C.POINTER(C.c_int)]),
+    "gs_grid_pcg_supported": (C.c_int, [C.c_void_p]),
+    "gs_grid_pcg_record": (C.c_int, [C.c_void_p, dptr, C.c_int]),
     "gs_grid_set_transfer": (C.c_int, [C.c_void_p, C.c_int]),
     "gs_grid_get_transfer": (C.c_int, [C.c_void_p]),
     "gs_grid_set_fmg_prolong": (C.c_int, [C.c_void_p, C.c_int]),
@@ -303,6 +326,12 @@ def transfer():
     return _load(TRANSFER_LIB, TRANSFER_API)
 
 
+def krylov():
+    """The PCG pass library (libgpusolve_krylov.so)."""
+    kernels()
+    return _load(KRYLOV_LIB, KRYLOV_API)
+
+
 def diag():
     """The diagnostics library (libgpusolve_diag.so): measurement and tuning code, never the product path."""
     kernels()
@@ -312,4 +341,5 @@ def diag():
 def driver():
     """The host driver library (libgpusolve_driver.so); loads the kernel libraries first."""
     transfer()
+    krylov()
     return _load(DRIVER_LIB, DRIVER_API)

@@ -57,6 +57,9 @@ void gs_grid_destroy(void* grid);
  *     exactly: the adoption of the speculative sweeps is undone); with GS_NO_PIPELINE or GS_NO_SPECULATION it has not.
  *     Upload a level's v and f (gs_grid_upload) or run a V-cycle from above it before reading it.
  *   - gs_grid_vcycle_level(l) reads level l's v and f and defines the levels below l; the levels above are not touched.
+ *   - gs_grid_pcg (and a gs_grid_solve that GS_SOLVER=pcg sends there) leaves level 0's v = x, the last complete
+ *     iteration's iterate, and level 0's f the caller's, word for word; v and f of the levels >= 1 are unspecified,
+ *     exactly as after a tol-stopped solve (the preconditioner's cycles ran on them, from the residual, not from f).
  *   - NEWTON: after a solve only level 0's newtonV is defined; v and f of every level are the inner solves' work fields.
  *   - every field is handed back stored: a zero iterate the driver keeps as a flag is never visible to gs_grid_download,
  *     and gs_grid_upload of a level's v is what the next operation on that level reads. */
@@ -76,6 +79,34 @@ int gs_grid_vcycle_level(void* grid, int level);
  * GS_FMG=k in the environment when the grid is created makes gs_grid_solve / GpuSolve-hip run this pass after the
  * initial-residual line. */
 int gs_grid_fmg(void* grid, int cycles_per_level, double* residual);
+/* Conjugate gradients preconditioned by the V-cycle (added). x0 = level 0's v as it stands (an
+ * upload or a preceding gs_grid_fmg is honoured), r = f - A x0, hist[0] = ||r||; then at most maxiter iterations
+ * (the grid's maxiter and tol; gs_grid_solve's stopping rule, history and *count semantics, and with `print` its
+ * "iter: k residual: r Took Nms" lines), each one V-cycle from a zero iterate on the residual (every fused, tiled,
+ * coarse-launch, weighted and POSITION path as gs_grid_vcycle takes it) plus three passes over level 0
+ * (gpusolve_krylov.h). hist[k] is the square root of the recurrence residual's r . r. The scalars stay on the device;
+ * the host waits once per iteration, for that norm. The first call allocates four more level-0 fields (r, z and two
+ * directions; q lives in the cycle's ping-pong partner); if that fails the call fails with nothing changed.
+ * Returns 0; GS_PCG_BREAKDOWN when p . q or r . z was not a positive finite number (a zero right-hand side, or a
+ * residual already at rounding level): the loop ends there, v and the history are those of the last complete
+ * iteration, nothing is NaN. The same code when an iteration's r . r is not finite (GS_PCG_BAD_RR: the iterate
+ * overflowed; v holds it and the history ends before it, so the 0 recorded for r . r never counts as converged).
+ * 1 (gs_last_error(), nothing touched) for a grid PCG cannot run on: a mode other than LINEAR, a Z-slab / RCCL or
+ * trace grid, pre != post or pre = 0, weights whose post weights are not a permutation of
+ * the pre weights, a stencil whose weight at offset o is not its weight at -o, a transition that is not aligned while
+ * the transfers are REFERENCE — each makes the cycle a non-symmetric or indefinite preconditioner.
+ * GS_SOLVER=pcg|vcycle in the environment when the grid is created makes gs_grid_solve / GpuSolve-hip on a LINEAR
+ * grid run this instead of the V-cycle loop (after GS_FMG=k: from FMG's iterate); an ineligible grid then fails the
+ * solve before any work, any other value fails the creation. */
+enum { GS_PCG_BREAKDOWN = 2 };
+int gs_grid_pcg(void* grid, int print, double* hist, int cap, int* count);
+/* 1 if gs_grid_pcg can run on the grid as it is configured now, else 0 and the reason in gs_last_error(). */
+int gs_grid_pcg_supported(void* grid);
+/* The last gs_grid_pcg run's scalars: returns the number n of iterations it started (a breakdown's included; -1 and
+ * gs_last_error() before any run) and writes, for k < min(n, cap_iters), rec[6k .. 6k+5] = r.z and p.q of iteration
+ * k, alpha = rz / pq, the beta its direction used (0 for k = 0, else rz_k / rz_(k-1)), the new r . r, and the flag
+ * (0, or GS_PCG_BAD_PQ | GS_PCG_BAD_RZ | GS_PCG_BAD_RR of gpusolve_krylov.h). rec may be NULL with cap_iters 0. */
+int gs_grid_pcg_record(void* grid, double* rec, int cap_iters);
 /* The level FMG starts on: the deepest level with every transition above it aligned (fine n = 2 coarse n + 1 per
  * axis); 0 when FMG is not applicable to the grid. */
 int gs_grid_fmg_start_level(void* grid);
