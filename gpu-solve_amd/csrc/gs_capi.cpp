@@ -238,6 +238,13 @@ int gs_grid_set_transfer(void* grid, int mode)
 
 int gs_grid_get_transfer(void* grid) { return G(grid).transferMode; }
 
+int gs_grid_set_smoother(void* grid, int mode)
+{
+    return guarded([&] { G(grid).setSmoother(mode); });
+}
+
+int gs_grid_get_smoother(void* grid) { return G(grid).smootherMode; }
+
 int gs_grid_set_fmg_prolong(void* grid, int mode)
 {
     return guarded([&] { G(grid).setFmgProlong(mode); });

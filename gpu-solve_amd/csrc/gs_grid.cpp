@@ -222,6 +222,16 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
             throw Error("GS_TRANSFER=" + t + ": the value must be position or reference");
     }
     if (transferEnv == 1 && (nranks() > 1 || traceLog)) throw Error(kTransferSingleGpu); // before any work or collective
+    // GS_SMOOTHER=zline|jacobi: the smoother (setSmoother, once the levels exist); anything else, and zline on a grid
+    // that cannot take it, throws here, before any work or collective
+    int smootherEnv = 0;
+    if (const char* e = std::getenv("GS_SMOOTHER")) {
+        const std::string t = e;
+        if (t == "zline") smootherEnv = 1;
+        else if (t != "jacobi")
+            throw Error("GS_SMOOTHER=" + t + ": the value must be zline or jacobi");
+    }
+    if (smootherEnv == 1) zlineCheck();
     // GS_FMG_PROLONG=position|aligned: full multigrid's prolongation (setFmgProlong, once the levels exist)
     int fmgProlongEnv = 0;
     if (const char* e = std::getenv("GS_FMG_PROLONG")) {
@@ -304,6 +314,7 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
     coarseFromRef_ = coarseFrom;
     xferT_.assign(levels_.size(), gs_transfer_tables{});
     fmgT_.assign(levels_.size(), gs_fmg_tables{});
+    zlineT_.assign(levels_.size(), gs_zline_tables{});
     if (mode == NEWTON) newtonF = DeviceField(levels_[0].geom.nx, levels_[0].geom.ny, levels_[0].geom.nz, s, dry);
     newtonVZero_ = mode == NEWTON; // (every field is created zero-filled)
     {
@@ -369,6 +380,7 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
     check((int)hipStreamSynchronize(s), "hipStreamSynchronize");
     if (transferEnv) setTransfer(transferEnv);
     if (fmgProlongEnv) setFmgProlong(fmgProlongEnv);
+    if (smootherEnv) setSmoother(smootherEnv);
 }
 
 bool HipGridData::levelAligned(std::size_t l) const
@@ -428,14 +440,66 @@ void HipGridData::setTransfer(int m)
         xferT_[l] = T;
     }
     transferMode = m;
-    // the one-launch coarse cycle embeds the index-aligned transfers: in POSITION mode it starts at the first level,
-    // from the reference rule's on, below which every transition is aligned (none: no coarse launch)
+    updateCoarseFrom();
+}
+
+// The one-launch coarse cycle embeds the index-aligned transfers and point Jacobi: in POSITION mode it starts at the
+// first level, from the reference rule's on, below which every transition is aligned (none: no coarse launch); in
+// ZLINE mode there is none.
+void HipGridData::updateCoarseFrom()
+{
+    const std::size_t nl = levels_.size();
     coarseFrom = coarseFromRef_;
-    if (m == 1 && coarseFromRef_ < nl) {
+    if (transferMode == 1 && coarseFromRef_ < nl) {
         std::size_t c = nl - 1;
         while (c > coarseFromRef_ && levelAligned(c - 1)) c--;
         coarseFrom = c;
     }
+    if (zline()) coarseFrom = nl;
+}
+
+void HipGridData::zlineCheck() const
+{
+    if (mode != LINEAR)
+        throw Error("smoother: ZLINE needs a LINEAR grid (NONLINEAR and NEWTON line sweeps are not built: their diagonal "
+                    "is a field)");
+    if (nranks() > 1 || trace)
+        throw Error("smoother: ZLINE needs a single-GPU grid (not a Z-slab / RCCL or schedule-trace grid: the lines "
+                    "cross the slabs)");
+    if (!gs_zline_supported(&stencilAbi))
+        throw Error("smoother: ZLINE needs a stencil of the seven axis offsets, once each, whose centre weight s0 is "
+                    "not 0 and has |s0| >= |weight at (0,0,+1)| + |weight at (0,0,-1)|");
+}
+
+void HipGridData::setSmoother(int m)
+{
+    if (m != 0 && m != 1) throw Error("smoother: the mode must be GS_SMOOTHER_JACOBI (0) or GS_SMOOTHER_ZLINE (1)");
+    if (m == 1) {
+        zlineCheck();
+        if (!zlineT_[0].cp) {
+            // one allocation: per level cp, then den (nz + 2 doubles each)
+            std::vector<double> host;
+            std::vector<std::size_t> at;
+            for (const auto& L : levels_) {
+                const std::size_t n = (std::size_t)L.geom.nz + 2;
+                at.push_back(host.size());
+                host.resize(host.size() + 2 * n);
+                check(gs_zline_factors(&stencilAbi, L.geom.nz, host.data() + at.back(), host.data() + at.back() + n),
+                      "gs_zline_factors");
+            }
+            double* base = nullptr;
+            check((int)hipMalloc((void**)&base, sizeof(double) * host.size()), "hipMalloc(z-line factors)");
+            xferMem_.push_back(base);
+            check((int)hipMemcpy(base, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice),
+                  "hipMemcpy(z-line factors)");
+            for (std::size_t l = 0; l < levels_.size(); l++) {
+                const int64_t nz = levels_[l].geom.nz;
+                zlineT_[l] = gs_zline_tables{base + at[l], base + at[l] + nz + 2, nz};
+            }
+        }
+    }
+    smootherMode = m;
+    updateCoarseFrom();
 }
 
 void HipGridData::setFmgProlong(int m)
@@ -913,9 +977,10 @@ void HipSolver::settleExchange(HipGridData& grid)
     if (!grid.trace) check((int)hipEventRecord(grid.evB_, grid.commStream()), "hipEventRecord");
 }
 
+// (the speculative step is a point sweep or pair: not in ZLINE mode)
 bool HipSolver::speculationEnabled(const HipGridData& grid)
 {
-    return grid.sw.speculation && grid.preSmoothing > 0 && grid.numLevels() > 1;
+    return grid.sw.speculation && grid.preSmoothing > 0 && grid.numLevels() > 1 && !grid.zline();
 }
 
 // src/cpu/CpuSolver.cpp:12-43. Every norm the loop reads (the initial one and each V-cycle's closing
@@ -1103,6 +1168,17 @@ void HipSolver::jacobi(HipGridData& grid, std::size_t l, std::size_t sweeps, con
 {
     auto& L = grid.getLevel(l);
     const hipStream_t s = grid.stream();
+    if (grid.zline()) {
+        // one z-line sweep per sweep (single GPU, whole levels: setSmoother): no pairs, no triples
+        for (; sweeps > 0; sweeps--) {
+            check(gs_zline_sweep(&grid.stencilAbi, &L.geom, w ? *w++ : grid.omega, L.vZero ? nullptr : L.v.data(),
+                                 L.vAlt.data(), L.f.data(), grid.zlineTables(l), s),
+                  "gs_zline_sweep");
+            L.v.swap(L.vAlt);
+            L.vZero = false;
+        }
+        return;
+    }
     const bool dist = L.distributed && grid.nranks() > 1;
     const int64_t nz = L.geom.nz;
     const int depth = grid.vDepth(L);
@@ -1286,7 +1362,8 @@ void HipSolver::upLeg(HipGridData& grid, std::size_t i)
     // (the tiled step fuses the prolongation with a pair: the GS_NO_FUSED_SWEEPS / GS_NO_FUSED_PROLONG
     // alternatives take the general path below)
     const bool pa = grid.pa(i - 1); // position-aware transfers: the general path below, with gs_prolong_add_pa
-    if (!pa && i - 1 >= 1 && F.tiled && !C.distributed && grid.postSmoothing >= 2 && grid.sw.fusedSweeps &&
+    const bool zl = grid.zline(); // z-line sweeps: neither fused step below, both embed point Jacobi
+    if (!pa && !zl && i - 1 >= 1 && F.tiled && !C.distributed && grid.postSmoothing >= 2 && grid.sw.fusedSweeps &&
         grid.sw.fusedProlong) {
         // a small level: prolongation, correction and the first two post-smoothing sweeps in one launch
         materialize(grid, i - 1);
@@ -1306,7 +1383,7 @@ void HipSolver::upLeg(HipGridData& grid, std::size_t i)
         grid.clock.mark(s, (int)(i - 1), false);
         return;
     }
-    if (!pa && grid.sw.fusedProlong && F.fusedPairs && grid.postSmoothing >= 2 && proWorthIt(grid, i - 1) && proSlabOk(grid, i - 1) &&
+    if (!pa && !zl && grid.sw.fusedProlong && F.fusedPairs && grid.postSmoothing >= 2 && proWorthIt(grid, i - 1) && proSlabOk(grid, i - 1) &&
         gs_jacobi_sweep2_prolong_supported(&grid.stencilAbi, &F.geom, (int)grid.mode)) {
         // the first two post-smoothing sweeps of v^h + P v^2h in one pass (the corrected
         // iterate is never stored), then the remaining ones. On a Z-slab each rank corrects its
@@ -1379,8 +1456,8 @@ void HipSolver::downFrom(HipGridData& grid, std::size_t from, int* pending)
         // (the tiled step fuses a pair, the residual and the restriction and leaves v^2h = 0 as a flag: the
         // GS_NO_FUSED_SWEEPS / GS_NO_FUSED_RR / GS_NO_ZERO_GUESS alternatives take the general path below)
         const bool pa = grid.pa(i); // position-aware transfers: the general path below with the _pa launchers
-        if (!pa && i >= 1 && pre == 2 && L.tiled && !C.distributed && grid.sw.fusedSweeps && grid.sw.fusedRR &&
-            grid.sw.zeroGuess) {
+        if (!pa && !grid.zline() && i >= 1 && pre == 2 && L.tiled && !C.distributed && grid.sw.fusedSweeps &&
+            grid.sw.fusedRR && grid.sw.zeroGuess) {
             // a small level: the pre-smoothing pair, residual and restriction in one tiled launch
             if (grid.trace)
                 grid.rec("tiledpre", {{"L", (long long)i}, {"vzero", L.vZero}});

@@ -22,6 +22,7 @@
 
 #include "gpusolve_hip.h"
 #include "gpusolve_transfer.h"
+#include "gpusolve_line.h"
 #include "gs_comm.hpp"
 #include "gs_params.hpp"
 
@@ -204,6 +205,22 @@ public:
     bool levelAligned(std::size_t l) const; // the transition l -> l + 1 (l + 1 < numLevels())
     bool pa(std::size_t l) const { return transferMode == 1 && !levelAligned(l); }
     const gs_transfer_tables* xfer(std::size_t l) const { return &xferT_[l]; }
+    // The smoother (gs_grid_set_smoother, GS_SMOOTHER). 0, the default (JACOBI): damped point Jacobi,
+    // every launch as before. 1 (ZLINE): HipSolver::jacobi runs one gs_zline_sweep (include/gpusolve_line.h) per sweep,
+    // v -> vAlt and a swap, NULL while vZero holds, omega from the weight cursor where weights are set. Everything that
+    // embeds point Jacobi is then not taken — the fused pairs and triples, the fused prolongation pair, the tiled
+    // steps, the one-launch coarse cycle (coarseFrom = numLevels()) and the speculative closing norm, with it the
+    // overlap of the norm wait with the next cycle: the norm comes from a residual pass, as under GS_NO_SPECULATION.
+    // What does not depend on the smoother stays: gs_residual_restrict, gs_prolong_add, the _pa launchers, the
+    // zero-guess flag. LINEAR single-GPU grids whose stencil gs_zline_supported accepts; with GS_TRANSFER, GS_FMG and
+    // GS_OMEGAS the switches that change the iterate.
+    int smootherMode = 0;
+    bool zline() const { return smootherMode == 1; }
+    // builds (gs_zline_factors) and uploads every level's factors the first time ZLINE is switched on; they are freed
+    // with the grid. Throws, leaving the grid as it was (zlineCheck: what a refusal says).
+    void setSmoother(int mode);
+    void zlineCheck() const;
+    const gs_zline_tables* zlineTables(std::size_t l) const { return &zlineT_[l]; }
     // Full multigrid's prolongation (gs_grid_set_fmg_prolong, GS_FMG_PROLONG). 0, the default (ALIGNED): gs_fmg_prolong
     // on aligned transitions only, so FMG starts at the deepest level above which every transition is aligned and is
     // refused where that is level 0. 1 (POSITION): FMG starts at the coarsest level; an aligned transition keeps
@@ -311,7 +328,9 @@ private:
     std::size_t coarseFromRef_ = 0;          // coarseFrom of the REFERENCE transfers (GS_COARSE_POINTS' rule)
     std::vector<gs_transfer_tables> xferT_;  // per transition l -> l + 1; null pointers where aligned or not built
     std::vector<gs_fmg_tables> fmgT_;        // the same for gs_fmg_prolong_pa
-    std::vector<void*> xferMem_;             // the device allocations behind both
+    std::vector<gs_zline_tables> zlineT_;    // per level: the z-line factors (null pointers until ZLINE is first set)
+    std::vector<void*> xferMem_;             // the device allocations behind all three
+    void updateCoarseFrom();                 // coarseFrom from coarseFromRef_, the transfers and the smoother
     bool haloPending_ = false; // an exchange issued by haloIssue, not settled
     friend class NewtonSolver;
     bool newtonR1_ = false;    // level 1's newtonVNext holds R(level 0's newtonV) (gs_newton_F_update_restrict)

@@ -24,6 +24,7 @@ from ._abi import GS_LINEAR, GS_MAX_WEIGHTS, GS_NEWTON, GS_NEWTON_B, GS_NEWTON_G
 from ._abi import GS_TRANSFER_POSITION, GS_TRANSFER_REFERENCE, gs_transfer_tables, transfer  # noqa: F401
 from ._abi import GS_FMG_PROLONG_ALIGNED, GS_FMG_PROLONG_POSITION, gs_fmg_tables  # noqa: F401
 from ._abi import GS_PCG_BREAKDOWN, krylov  # noqa: F401
+from ._abi import GS_SMOOTHER_JACOBI, GS_SMOOTHER_ZLINE, gs_zline_tables, line  # noqa: F401
 
 CANONICAL_OFFSETS = [(0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)]
 
@@ -110,6 +111,7 @@ def _check(rc: int):
 
 _TRANSFERS = {"reference": GS_TRANSFER_REFERENCE, "position": GS_TRANSFER_POSITION}
 _FMG_PROLONGS = {"aligned": GS_FMG_PROLONG_ALIGNED, "position": GS_FMG_PROLONG_POSITION}
+_SMOOTHERS = {"jacobi": GS_SMOOTHER_JACOBI, "zline": GS_SMOOTHER_ZLINE}
 FIELDS = {"v": 0, "restV": 1, "newtonV": 2, "f": 3, "r": 4, "newtonF": 5}
 
 
@@ -201,6 +203,22 @@ class HipGridData:
         """The transfer mode in force (set_transfer or GS_TRANSFER): "reference" or "position"."""
         m = driver().gs_grid_get_transfer(self.handle)
         return next(k for k, v in _TRANSFERS.items() if v == m)
+
+    def set_smoother(self, mode: str):
+        """The smoother of every sweep: "jacobi" (the default: damped point Jacobi) or "zline" (each sweep solves every
+        z-column's tridiagonal system exactly and stays Jacobi across columns: include/gpusolve_line.h) — for stencils
+        whose z weights dominate, where point Jacobi V-cycles stall; no gain on an isotropic stencil or a weak z axis.
+        solve, vcycle, vcycle_from, jacobi, fmg and pcg follow it. GpuSolveError, with nothing changed, on a grid that
+        is not LINEAR, on a Z-slab grid, and for a stencil gs_zline_supported refuses."""
+        if mode not in _SMOOTHERS:
+            raise ValueError(f"smoother must be one of {sorted(_SMOOTHERS)}")
+        _check(driver().gs_grid_set_smoother(self.handle, _SMOOTHERS[mode]))
+
+    @property
+    def smoother(self) -> str:
+        """The smoother in force (set_smoother or GS_SMOOTHER): "jacobi" or "zline"."""
+        m = driver().gs_grid_get_smoother(self.handle)
+        return next(k for k, v in _SMOOTHERS.items() if v == m)
 
     def set_fmg_prolong(self, mode: str):
         """Full multigrid's prolongation: "aligned" (the default: HipSolver.fmg needs sizes 2^k - 1) or "position"

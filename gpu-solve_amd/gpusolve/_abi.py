@@ -13,6 +13,7 @@ BIN_DIR = os.path.join(PKG_ROOT, "bin")
 KERNEL_LIB = os.path.join(LIB_DIR, "libgpusolve_hip.so")
 TRANSFER_LIB = os.path.join(LIB_DIR, "libgpusolve_transfer.so")  # position-aware transfers (include/gpusolve_transfer.h)
 KRYLOV_LIB = os.path.join(LIB_DIR, "libgpusolve_krylov.so")  # the PCG passes (include/gpusolve_krylov.h)
+LINE_LIB = os.path.join(LIB_DIR, "libgpusolve_line.so")  # the z-line smoother (include/gpusolve_line.h)
 DIAG_LIB = os.path.join(LIB_DIR, "libgpusolve_diag.so")  # tools/ and tests/ only (include/gpusolve_diag.h)
 DRIVER_LIB = os.path.join(LIB_DIR, "libgpusolve_driver.so")
 EXECUTABLE = os.path.join(BIN_DIR, "GpuSolve-hip")
@@ -23,6 +24,7 @@ GS_NEWTON_G = 4  # GS_NEWTON_B whose factor field holds gamma everywhere (the fi
 GS_EINVAL = 100001
 GS_TRANSFER_REFERENCE, GS_TRANSFER_POSITION = 0, 1  # gs_grid_set_transfer (include/gpusolve_driver.h)
 GS_FMG_PROLONG_ALIGNED, GS_FMG_PROLONG_POSITION = 0, 1  # gs_grid_set_fmg_prolong (include/gpusolve_driver.h)
+GS_SMOOTHER_JACOBI, GS_SMOOTHER_ZLINE = 0, 1  # gs_grid_set_smoother (include/gpusolve_driver.h)
 # include/gpusolve_krylov.h: the record's layout, its flag bits, and what gs_pcg_scalars does
 GS_PCG_RZ_I, GS_PCG_PQ_I, GS_PCG_ALPHA_I, GS_PCG_BETA_I, GS_PCG_RR_I, GS_PCG_FLAG_I, GS_PCG_REC = 0, 1, 2, 3, 4, 5, 8
 GS_PCG_BAD_PQ, GS_PCG_BAD_RZ, GS_PCG_BAD_RR = 1, 2, 4
@@ -61,6 +63,11 @@ class gs_transfer_tables(C.Structure):
 class gs_fmg_tables(C.Structure):
     """include/gpusolve_transfer.h: nf / nc per axis (host metadata), then device pointers per axis."""
     _fields_ = [("nf", i64 * 3), ("nc", i64 * 3), ("cj", C.c_void_p * 3), ("cw", C.c_void_p * 3)]
+
+
+class gs_zline_tables(C.Structure):
+    """include/gpusolve_line.h: device pointers to cp and den (nz + 2 doubles each) and the nz they were built for."""
+    _fields_ = [("cp", C.c_void_p), ("den", C.c_void_p), ("nz", i64)]
 
 
 # name -> (restype, argtypes); void* is used for device pointers and streams
@@ -204,6 +211,15 @@ KRYLOV_API = {
     "gs_pcg_scalars": (C.c_int, [C.c_int, C.c_void_p, i64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# libgpusolve_line.so (include/gpusolve_line.h): the z-line Jacobi smoother
+LINE_API = {
+    "gs_zline_supported": (C.c_int, [C.POINTER(gs_stencil)]),
+    "gs_zline_factors": (C.c_int, [C.POINTER(gs_stencil), i64, dptr, dptr]),
+    "gs_zline_sweep": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_double, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.POINTER(gs_zline_tables), C.c_void_p]),
+    "gs_zline_kernel": (C.c_char_p, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int]),
+}
+
 DRIVER_API = {
     "gs_parse_config": (C.c_int, [C.c_char_p, C.POINTER(gs_params)]),
     "gs_grid_create": (C.c_void_p, [C.POINTER(gs_params)]),
@@ -218,6 +234,8 @@ DRIVER_API = {
     "gs_grid_pcg_record": (C.c_int, [C.c_void_p, dptr, C.c_int]),
     "gs_grid_set_transfer": (C.c_int, [C.c_void_p, C.c_int]),
     "gs_grid_get_transfer": (C.c_int, [C.c_void_p]),
+    "gs_grid_set_smoother": (C.c_int, [C.c_void_p, C.c_int]),
+    "gs_grid_get_smoother": (C.c_int, [C.c_void_p]),
     "gs_grid_set_fmg_prolong": (C.c_int, [C.c_void_p, C.c_int]),
     "gs_grid_get_fmg_prolong": (C.c_int, [C.c_void_p]),
     "gs_grid_level_aligned": (C.c_int, [C.c_void_p, C.c_int]),
@@ -332,6 +350,12 @@ def krylov():
     return _load(KRYLOV_LIB, KRYLOV_API)
 
 
+def line():
+    """The z-line smoother library (libgpusolve_line.so)."""
+    kernels()
+    return _load(LINE_LIB, LINE_API)
+
+
 def diag():
     """The diagnostics library (libgpusolve_diag.so): measurement and tuning code, never the product path."""
     kernels()
@@ -342,4 +366,5 @@ def driver():
     """The host driver library (libgpusolve_driver.so); loads the kernel libraries first."""
     transfer()
     krylov()
+    line()
     return _load(DRIVER_LIB, DRIVER_API)

@@ -147,6 +147,25 @@ int gs_parse_omegas(const char* text, int pre, int post, double* out);
 enum { GS_TRANSFER_REFERENCE = 0, GS_TRANSFER_POSITION = 1 };
 int gs_grid_set_transfer(void* grid, int mode);
 int gs_grid_get_transfer(void* grid);
+/* The smoother (added). GS_SMOOTHER_JACOBI, the default: damped point Jacobi, every launch as
+ * before. GS_SMOOTHER_ZLINE: every sweep solves each z-column's tridiagonal system exactly and stays Jacobi across
+ * columns (gs_zline_sweep of gpusolve_line.h, one launch per sweep) — the smoother for a stencil whose z weights
+ * dominate (thin cells in z), where point Jacobi V-cycles stall; on an isotropic stencil, or one whose weak axis is z,
+ * it gains nothing and costs about four point cycles per cycle. A strong x or y axis: order the axes so that it is z.
+ * In ZLINE mode nothing that embeds point Jacobi is taken (the fused pairs and triples, the fused prolongation pair,
+ * the tiled steps, the one-launch coarse cycle, the speculative closing norm and with it the overlap of the norm wait
+ * with the next cycle: the norm comes from a residual pass); the residual + restriction, the prolongation, the
+ * POSITION transfers and the zero-guess flag are unchanged. gs_grid_solve, gs_grid_vcycle, gs_grid_vcycle_level,
+ * gs_grid_jacobi, gs_grid_fmg and gs_grid_pcg follow the grid's smoother (per-sweep weights apply to line sweeps as
+ * to point sweeps; a z-line cycle with pre = post is symmetric, so gs_grid_pcg's conditions are unchanged). Switching
+ * back to JACOBI restores every launch of the default path. The factors of every level are built and uploaded when
+ * ZLINE is first switched on and freed with the grid. Fails (return 1, gs_last_error(), nothing changed) for any
+ * other mode value and for ZLINE on a grid that is not LINEAR, on a Z-slab / RCCL or schedule-trace grid (the lines
+ * cross the slabs) and for a stencil gs_zline_supported refuses. GS_SMOOTHER=zline|jacobi in the environment when the
+ * grid is created sets the mode; any other value, and zline on such a grid, fails the creation. */
+enum { GS_SMOOTHER_JACOBI = 0, GS_SMOOTHER_ZLINE = 1 };
+int gs_grid_set_smoother(void* grid, int mode);
+int gs_grid_get_smoother(void* grid);
 /* Full multigrid's prolongation (added; DESIGN.md §4.7 "FMG on every size"). GS_FMG_PROLONG_ALIGNED, the default:
  * gs_grid_fmg as described above, unchanged launch for launch. GS_FMG_PROLONG_POSITION: gs_grid_fmg_start_level is the
  * coarsest level on every LINEAR / NONLINEAR single-GPU grid (NEWTON, Z-slab and trace grids: still 0, still refused);
