@@ -39,6 +39,8 @@
 //                 (the field lies gs_exp_set_efoff(n) elements past newtonV; tools/newton_kprobe.py sets it)
 //   GS_EXP_T3_FLIGHT k_tb3y's sweep 1 takes its z+ operand, row -2 and f from planes already in registers, so no stage
 //                 waits on the newest loads (bounds what more flight time for the loads can buy)
+//   GS_EXP_T3_SYM    k_tb3y's whole-wave-rows instance keeps the symmetric step (both y-waves in phase: what the
+//                    stagger of waves 4-7 is worth)
 //   GS_EXP_T3_CHAIN  k_tb3y's sweeps 2 and 3 take their z+ operand from the previous step's plane instead of the stage
 //                 before them (bounds what breaking the stage-to-stage chain can buy)
 // Alternative-arithmetic builds (A/B only; correct results, not the product's choice):
@@ -3019,6 +3021,16 @@ constexpr int tby_pfd(int mode) { return mode == GS_LINEAR ? 2 : 1; }
 // planes, both sweep-2 planes and both load slots are live), and batched there the unit-stencil instances spill.
 // Each quotient is the same value either way. The unit-stencil instances are batched (254 / 256 VGPRs with per-lane
 // addresses), the general-stencil instance is not (256, its sums through stencil_sum_in_order).
+// ST (the scalar-base instance for rows of whole waves, the 512^3 benchmark's): the two y-waves that share a SIMD (waves
+// i and i+4, the same wx) run out of phase. wy = 0 keeps the step above. wy = 1 lags by half a step: between barriers z
+// and z+1 it runs sweep 1 at plane z FIRST (the plane wy = 0 evaluated at the end of the previous interval), issues its
+// loads into the slot that sweep 1 consumed, then runs sweep 2 at z-1 (its z+ operand is the sweep 1 just computed)
+// and sweep 3 at z-2; so one half's load issue, load wait and store burst sit beside the other's arithmetic. Still one
+// barrier per step and publish -> barrier -> read; at barrier z both halves hold sweep-1(z-1) and sweep-2(z-2) as
+// before. Only the exchanged v row differs: wy = 0 publishes v(z) (its Vp), wy = 1 v(z+1) from the load slot it has not
+// consumed yet. The lagging half runs its own copy of the whole z loop (`half` below): in one loop with a branch per
+// step each half carries the other's state through its steps as live values, the two do not fit 256 VGPRs together,
+// and loads issued on one path only turn the compiler's counted vmcnt waits into vmcnt(0) where the paths join.
 // GS_EXP_T3_FLIGHT / GS_EXP_T3_CHAIN: the two timing-only probes of the step's shape (top of this file).
 #ifdef GS_EXP_T3_CHAIN
 #define GS_T3_ZP(n, c) c
@@ -3037,6 +3049,11 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
     constexpr int NE = N0 + N1 + RY; // x-edge values per wave side: v rows -1..RY, sweep-1 rows 0..RY, sweep-2 rows 1..RY
     constexpr int B1 = DB ? (SA ? N0 : 2) : 1, B2 = DB ? N1 : 1, B3 = 1; // rows per division batch of sweeps 1, 2, 3
     constexpr bool RS = SA; // the previous-plane rows of sweeps 1 / 2 and sweep 3's f in registers, not in LDS
+#ifdef GS_EXP_T3_SYM
+    constexpr bool ST = false;
+#else
+    constexpr bool ST = SA && FX; // the staggered step: the mirrored y-waves (wy = 1) run half a step behind (above)
+#endif
     // x-edges: [parity][y-wave][1 + x-wave][side][value]; x-wave slots 0 and WX+1 are the zero x-boundary columns
     __shared__ double edge[2][2][WXMAX + 2][2][NE];
     // y-edge rows: [parity][y-wave][x-wave][v | sweep-1 | sweep-2][lane]
@@ -3064,253 +3081,312 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
     const int y0 = 1 + (int)(tile % gridDim.x) * (2 * RY);
     const int zb = 1 + (int)(tile / gridDim.x) * ZC;
     const int ze = min(zb + ZC - 1, nz);
-    const bool mir = wy != 0;
-    auto yof = [&](int j) { return mir ? y0 + 2 * RY - j : y0 - 1 + j; };
+    // The rest of the kernel once per half: the lagging waves (ST: the mirrored y-waves) run their own copy of the z
+    // loop around the same barriers, so that neither half carries the other's state through its steps; what joins
+    // the halves is the LDS protocol alone
+    auto half = [&](auto lagc) {
+        constexpr bool LAG = decltype(lagc)::get();
+        const bool mir = LAG || (!ST && wy != 0);
+        auto yof = [&](int j) { return mir ? y0 + 2 * RY - j : y0 - 1 + j; };
 
-    int64_t roff[RY + 3]; // local rows j = -2..RY at index j+2
-    bool rowc[RY + 3];
+        int64_t roff[RY + 3]; // local rows j = -2..RY at index j+2
+        bool rowc[RY + 3];
 #pragma unroll
-    for (int j = -2; j <= RY; j++) {
-        const int y = yof(j);
-        roff[j + 2] = (int64_t)min(max(y, 0), ny + 1) * ldy;
-        rowc[j + 2] = y >= 1 && y <= ny;
-    }
-    const bool in1 = rowc[1] && rowc[2] && rowc[3] && rowc[4]; // every sweep-1 / sweep-2 row is an interior row
-    const bool in2 = rowc[2] && rowc[3] && rowc[4];
-    auto planeok = [&](int z) { return z >= 1 && z <= nz; };
-    auto cz = [&](int z) { return min(max(z, 0), nz + 1); }; // planes below 0 / above nz+1 are never dereferenced
-    auto at = [&](const double* base, int j, int z) { return base + xl + roff[j + 2] + (int64_t)z * ldz; };
-    // SA: the row's base on the scalar unit, the lane's byte offset in one VGPR (sa_base above). A lane that stores
-    // has x <= nx, so xl == x there and the stores take the loads' offset.
-    unsigned xo = 8u * (unsigned)xl;
-    auto ldrow = [&](const double* base, int j, int z) {
-        if constexpr (SA) return sa_ld2(sa_base(base + roff[j + 2] + (int64_t)z * ldz), xo);
-        else return ld2(at(base, j, z));
-    };
-
-    double2 Vp[N0], Vc[N0], VL[2][N0], FL[2][N0], HL[2]; // v(z), v(z+1); per slot: v(z+2), f(z+1), v(z+1) at row -2
-    double2 S1a[N0], S1c[N0], S2c[N1];                   // sweep 1 at planes z and z-1, sweep 2 at plane z-2
-    double2 S1p[N1], S2p[RY], F2[RY];                    // RS: sweep 1 at plane z-2, sweep 2 at plane z-3, f at plane z-2
-#pragma unroll
-    for (int i = 0; i < N0; i++) S1a[i] = S1c[i] = make_double2(0.0, 0.0);
-#pragma unroll
-    for (int i = 0; i < N1; i++) {
-        S2c[i] = make_double2(0.0, 0.0);
-        f1_l[0][i][wid][lane] = f1_l[1][i][wid][lane] = make_double2(0.0, 0.0);
-        if constexpr (RS) S1p[i] = make_double2(0.0, 0.0);
-        else s1p_l[i][wid][lane] = make_double2(0.0, 0.0);
-    }
-#pragma unroll
-    for (int i = 0; i < RY; i++) {
-        if constexpr (RS) {
-            S2p[i] = F2[i] = make_double2(0.0, 0.0);
-        } else {
-            f2_l[i][wid][lane] = make_double2(0.0, 0.0);
-            s2p_l[i][wid][lane] = make_double2(0.0, 0.0);
+        for (int j = -2; j <= RY; j++) {
+            const int y = yof(j);
+            roff[j + 2] = (int64_t)min(max(y, 0), ny + 1) * ldy;
+            rowc[j + 2] = y >= 1 && y <= ny;
         }
-    }
-    // a step's loads grouped by field, rows ascending (as the LINEAR plain pair, GRP)
-    auto load_slot = [&](const int s, const int z, const int zv) {
-        HL[s] = ldrow(v, -2, z);
-#pragma unroll
-        for (int i = 0; i < N0; i++) VL[s][i] = ldrow(v, i - 1, zv);
-#pragma unroll
-        for (int i = 0; i < N0; i++) FL[s][i] = ldrow(f, i - 1, z);
-    };
-#pragma unroll
-    for (int i = 0; i < N0; i++) {
-        Vp[i] = ldrow(v, i - 1, cz(zb - 3));
-        Vc[i] = ldrow(v, i - 1, cz(zb - 2));
-    }
-    load_slot(1, cz(zb - 2), cz(zb - 1));
-    for (int z0 = zb - 3; z0 <= ze + 2; z0 += 2) {
-#pragma unroll
-        for (int ph = 0; ph < 2; ph++) {
-            const int z = z0 + ph; // (a step past ze+2 loads clamped planes and stores nothing)
-            const int cs = ph ^ 1; // slot holding this step's operands
-            if constexpr (SA) xo = sa_lane(xo);
-            load_slot(ph, cz(z + 2), cz(z + 3));
-            // ---- publish: x-edge columns of the three stages and the y-edge rows
-            if (lane == 0) {
-#pragma unroll
-                for (int i = 0; i < N0; i++) edge[ph][wy][wx + 1][0][i] = Vc[i].x;
-#pragma unroll
-                for (int i = 0; i < N1; i++) edge[ph][wy][wx + 1][0][N0 + i] = S1c[i + 1].x;
-#pragma unroll
-                for (int i = 0; i < RY; i++) edge[ph][wy][wx + 1][0][N0 + N1 + i] = S2c[i + 1].x;
-            }
-            if (lane == WAVE - 1) {
-#pragma unroll
-                for (int i = 0; i < N0; i++) edge[ph][wy][wx + 1][1][i] = Vc[i].y;
-#pragma unroll
-                for (int i = 0; i < N1; i++) edge[ph][wy][wx + 1][1][N0 + i] = S1c[i + 1].y;
-#pragma unroll
-                for (int i = 0; i < RY; i++) edge[ph][wy][wx + 1][1][N0 + N1 + i] = S2c[i + 1].y;
-            }
-            yrow[ph][wy][wx][0][lane] = Vc[N0 - 1];
-            yrow[ph][wy][wx][1][lane] = S1c[N0 - 1];
-            yrow[ph][wy][wx][2][lane] = S2c[N1 - 1];
-            // LDS-only barrier: the outstanding prefetch stays in flight across it
-            GS_LDS_BARRIER();
-            // the x-edge values of the neighbour waves: read where a row uses them (an LDS broadcast read straight into
-            // the VGPRs the DPP shift takes as its old operand; all NE pairs read up front spill)
-            const double* const CL = edge[ph][wy][wx][1];
-            const double* const CR = edge[ph][wy][wx + 2][0];
-            const double2 vY = yrow[ph][wy ^ 1][wx][0][lane];  // v(z) at local row RY+1
-            const double2 s1Y = yrow[ph][wy ^ 1][wx][1][lane]; // sweep-1(z-1) at local row RY+1
-            const double2 s2Y = yrow[ph][wy ^ 1][wx][2][lane]; // sweep-2(z-2) at local row RY+1
+        const bool in1 = rowc[1] && rowc[2] && rowc[3] && rowc[4]; // every sweep-1 / sweep-2 row is an interior row
+        const bool in2 = rowc[2] && rowc[3] && rowc[4];
+        auto planeok = [&](int z) { return z >= 1 && z <= nz; };
+        auto cz = [&](int z) { return min(max(z, 0), nz + 1); }; // planes below 0 / above nz+1 are never dereferenced
+        auto at = [&](const double* base, int j, int z) { return base + xl + roff[j + 2] + (int64_t)z * ldz; };
+        // SA: the row's base on the scalar unit, the lane's byte offset in one VGPR (sa_base above). A lane that stores
+        // has x <= nx, so xl == x there and the stores take the loads' offset.
+        unsigned xo = 8u * (unsigned)xl;
+        auto ldrow = [&](const double* base, int j, int z) {
+            if constexpr (SA) return sa_ld2(sa_base(base + roff[j + 2] + (int64_t)z * ldz), xo);
+            else return ld2(at(base, j, z));
+        };
 
-            // one row of one stage in two halves around the division: the stencil sums of the lane's two points from
-            // the row's centre, its y- and z-neighbour rows and the x-edge values of the wave; then the new values
-            auto row_sums = [&](auto mirc, const double2 c, const double2 lm, const double2 lp, const double2 zm,
-                                const double2 zp, const double el, const double er, double& q0, double& q1) {
-                constexpr bool M = decltype(mirc)::get();
-                const double2 ym = M ? lp : lm, yp = M ? lm : lp;
-                const double xm0 = lane_from_left<true>(c.y, el);
-                const double xp1 = lane_from_right<true>(c.x, er);
-                if constexpr (UN) {
-                    q0 = stencil_sum<true>(k, c.x, c.y, xm0, yp.x, ym.x, zp.x, zm.x);
-                    q1 = stencil_sum<true>(k, c.y, xp1, c.x, yp.y, ym.y, zp.y, zm.y);
-                } else {
-                    q0 = stencil_sum_in_order(k, c.x, c.y, xm0, yp.x, ym.x, zp.x, zm.x);
-                    q1 = stencil_sum_in_order(k, c.y, xp1, c.x, yp.y, ym.y, zp.y, zm.y);
+        double2 Vp[N0], Vc[N0], VL[2][N0], FL[2][N0], HL[2]; // v(z), v(z+1); per slot: v(z+2), f(z+1), v(z+1) at row -2
+        double2 S1a[N0], S1c[N0], S2c[N1];                   // sweep 1 at planes z and z-1, sweep 2 at plane z-2
+        double2 S1p[N1], S2p[RY], F2[RY];                    // RS: sweep 1 at plane z-2, sweep 2 at plane z-3, f at plane z-2
+#pragma unroll
+        for (int i = 0; i < N0; i++) S1a[i] = S1c[i] = make_double2(0.0, 0.0);
+#pragma unroll
+        for (int i = 0; i < N1; i++) {
+            S2c[i] = make_double2(0.0, 0.0);
+            f1_l[0][i][wid][lane] = f1_l[1][i][wid][lane] = make_double2(0.0, 0.0);
+            if constexpr (RS) S1p[i] = make_double2(0.0, 0.0);
+            else s1p_l[i][wid][lane] = make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int i = 0; i < RY; i++) {
+            if constexpr (RS) {
+                S2p[i] = F2[i] = make_double2(0.0, 0.0);
+            } else {
+                f2_l[i][wid][lane] = make_double2(0.0, 0.0);
+                s2p_l[i][wid][lane] = make_double2(0.0, 0.0);
+            }
+        }
+        // a step's loads grouped by field, rows ascending (as the LINEAR plain pair, GRP)
+        auto load_slot = [&](const int s, const int z, const int zv) {
+            HL[s] = ldrow(v, -2, z);
+#pragma unroll
+            for (int i = 0; i < N0; i++) VL[s][i] = ldrow(v, i - 1, zv);
+#pragma unroll
+            for (int i = 0; i < N0; i++) FL[s][i] = ldrow(f, i - 1, z);
+        };
+        // (a lagging wave enters one plane behind and with both slots filled: its first sweep 1 consumes slot 1, the
+        // second slot 0, and each refills the slot it has consumed)
+        constexpr int zl = LAG ? 1 : 0;
+#pragma unroll
+        for (int i = 0; i < N0; i++) {
+            Vp[i] = ldrow(v, i - 1, cz(zb - 3 - zl));
+            Vc[i] = ldrow(v, i - 1, cz(zb - 2 - zl));
+        }
+        // (the scheduling fences keep the row bases of the prologue's 26 loads from being formed all at once: together
+        // they do not fit the SGPRs)
+        if constexpr (ST) __builtin_amdgcn_sched_barrier(0);
+        load_slot(1, cz(zb - 2 - zl), cz(zb - 1 - zl));
+        if constexpr (LAG) {
+            __builtin_amdgcn_sched_barrier(0);
+            load_slot(0, cz(zb - 1 - zl), cz(zb - zl));
+        }
+        // The lagging half is also the younger half of the block (waves 4-7), which loses the VALU arbitration against its
+        // SIMD partner at equal priority (priority first, then age), and its sweep 1 -> sweep 2 chain is the longer one:
+        // one static priority raise, no flips inside the loop. Worth 2.4 % on top of the stagger at 512^3 and 0.5 %
+        // without it (profiles/sweep3_stagger/summary.md)
+        if constexpr (LAG) __builtin_amdgcn_s_setprio(1);
+        for (int z0 = zb - 3; z0 <= ze + 2; z0 += 2) {
+#pragma unroll
+            for (int ph = 0; ph < 2; ph++) {
+                const int z = z0 + ph; // (a step past ze+2 loads clamped planes and stores nothing)
+                const int cs = ph ^ 1; // slot holding this step's operands
+                if constexpr (SA) xo = sa_lane(xo);
+                if constexpr (!LAG) load_slot(ph, cz(z + 2), cz(z + 3));
+                // ---- publish: x-edge columns of the three stages and the y-edge rows
+                if (lane == 0) {
+#pragma unroll
+                    for (int i = 0; i < N0; i++) edge[ph][wy][wx + 1][0][i] = Vc[i].x;
+#pragma unroll
+                    for (int i = 0; i < N1; i++) edge[ph][wy][wx + 1][0][N0 + i] = S1c[i + 1].x;
+#pragma unroll
+                    for (int i = 0; i < RY; i++) edge[ph][wy][wx + 1][0][N0 + N1 + i] = S2c[i + 1].x;
                 }
-            };
-            auto row_finish = [&](const double om, const double2 c, const double q0, const double q1, const double2 fv) {
-                const double a0 = op_finish<MODE>(k, q0, c.x, 0.0);
-                const double a1 = op_finish<MODE>(k, q1, c.y, 0.0);
-                return make_double2(jacobi_update<MODE>(k, c.x, fv.x - a0, 0.0, om),
-                                    jacobi_update<MODE>(k, c.y, fv.y - a1, 0.0, om));
-            };
-            auto kept = [&](const bool keep, const double2 c, const double2 n) {
-                return make_double2((keep || bx0) ? c.x : n.x, (keep || bx1) ? c.y : n.y);
-            };
-            // ---- the three sweeps; wave 1 (mirrored rows) runs its own copy of the code. The keep selects run only
-            // where some row, column or the plane is a boundary (a wave-uniform branch)
-            // sweep 1 at plane z+1, sweep 2 at plane z-1; F1: f at plane z-1 as sweep 2 read it (-> f2_l)
-            double2 S1n[N0], S2n[N1], F1[N1];
-            const bool pz0 = planeok(z + 1), pz1 = planeok(z - 1);
-            static_assert(N0 % B1 == 0 && N1 % B2 == 0 && RY % B3 == 0, "whole division batches");
-            // sweep 1 at plane z+1, local rows -1..RY
-            auto sweep1 = [&](auto mirc) {
+                if (lane == WAVE - 1) {
 #pragma unroll
-                for (int b = 0; b < N0; b += B1) {
-                    double q[2 * B1];
+                    for (int i = 0; i < N0; i++) edge[ph][wy][wx + 1][1][i] = Vc[i].y;
 #pragma unroll
-                    for (int i = b; i < b + B1; i++)
-#ifdef GS_EXP_T3_FLIGHT
-                        row_sums(mirc, Vc[i], i == 0 ? Vc[1] : Vc[i - 1], i == N0 - 1 ? vY : Vc[i + 1], Vp[i], Vp[i],
-                                 CL[i], CR[i], q[2 * (i - b)], q[2 * (i - b) + 1]);
-#else
-                        row_sums(mirc, Vc[i], i == 0 ? HL[cs] : Vc[i - 1], i == N0 - 1 ? vY : Vc[i + 1], Vp[i], VL[cs][i],
-                                 CL[i], CR[i], q[2 * (i - b)], q[2 * (i - b) + 1]);
-#endif
-                    div_hh_mm(k, q);
+                    for (int i = 0; i < N1; i++) edge[ph][wy][wx + 1][1][N0 + i] = S1c[i + 1].y;
 #pragma unroll
-                    for (int i = b; i < b + B1; i++)
-#ifdef GS_EXP_T3_FLIGHT
-                        S1n[i] = row_finish(k.omega[0], Vc[i], q[2 * (i - b)], q[2 * (i - b) + 1], Vp[i]);
-#else
-                        S1n[i] = row_finish(k.omega[0], Vc[i], q[2 * (i - b)], q[2 * (i - b) + 1], FL[cs][i]);
-#endif
+                    for (int i = 0; i < RY; i++) edge[ph][wy][wx + 1][1][N0 + N1 + i] = S2c[i + 1].y;
                 }
-                if (!FX || !pz0 || !in1) {
-#pragma unroll
-                    for (int i = 0; i < N0; i++) S1n[i] = kept(!pz0 || !rowc[i + 1], Vc[i], S1n[i]);
-                }
-            };
-            // sweep 2 at plane z-1, local rows 0..RY
-            auto sweep2 = [&](auto mirc) {
-#pragma unroll
-                for (int b = 0; b < N1; b += B2) {
-                    double q[2 * B2];
-#pragma unroll
-                    for (int i = b; i < b + B2; i++) {
-                        F1[i] = f1_l[ph][i][wid][lane];
-                        row_sums(mirc, S1c[i + 1], S1c[i], i == N1 - 1 ? s1Y : S1c[i + 2],
-                                 RS ? S1p[i] : s1p_l[i][wid][lane],
-                                 GS_T3_ZP(S1a[i + 1], S1c[i + 1]),
-                                 CL[N0 + i], CR[N0 + i], q[2 * (i - b)], q[2 * (i - b) + 1]);
+                // ST: the other half's sweep 1 runs one plane off this wave's. The leading wave hands over v(z), the
+                // lagging wave v(z+1) from the slot its next sweep 1 consumes (issued more than a step ago: the counted
+                // wait in front of this write leaves the newer slot's loads in flight)
+                if constexpr (LAG) yrow[ph][wy][wx][0][lane] = VL[cs][N0 - 1];
+                else yrow[ph][wy][wx][0][lane] = ST ? Vp[N0 - 1] : Vc[N0 - 1];
+                yrow[ph][wy][wx][1][lane] = S1c[N0 - 1];
+                yrow[ph][wy][wx][2][lane] = S2c[N1 - 1];
+                // LDS-only barrier: the outstanding prefetch stays in flight across it
+                GS_LDS_BARRIER();
+                // the x-edge values of the neighbour waves: read where a row uses them (an LDS broadcast read straight into
+                // the VGPRs the DPP shift takes as its old operand; all NE pairs read up front spill)
+                const double* const CL = edge[ph][wy][wx][1];
+                const double* const CR = edge[ph][wy][wx + 2][0];
+                // local row RY+1 of v(z+1) (a lagging wave: v(z)), sweep-1(z-1) and sweep-2(z-2): read here, ahead of their
+                // use (read by the sweep that uses them the staggered step is 7 % slower); the general-stencil instance
+                // reads each where it is used, up front it spills 2 VGPRs
+                constexpr bool YL = !UN;
+                const double2(&YR)[3][WAVE] = yrow[ph][wy ^ 1][wx];
+                double2 vY, s1Y, s2Y;
+                if constexpr (!YL) vY = YR[0][lane], s1Y = YR[1][lane], s2Y = YR[2][lane];
+
+                // one row of one stage in two halves around the division: the stencil sums of the lane's two points from
+                // the row's centre, its y- and z-neighbour rows and the x-edge values of the wave; then the new values
+                auto row_sums = [&](auto mirc, const double2 c, const double2 lm, const double2 lp, const double2 zm,
+                                    const double2 zp, const double el, const double er, double& q0, double& q1) {
+                    constexpr bool M = decltype(mirc)::get();
+                    const double2 ym = M ? lp : lm, yp = M ? lm : lp;
+                    const double xm0 = lane_from_left<true>(c.y, el);
+                    const double xp1 = lane_from_right<true>(c.x, er);
+                    if constexpr (UN) {
+                        q0 = stencil_sum<true>(k, c.x, c.y, xm0, yp.x, ym.x, zp.x, zm.x);
+                        q1 = stencil_sum<true>(k, c.y, xp1, c.x, yp.y, ym.y, zp.y, zm.y);
+                    } else {
+                        q0 = stencil_sum_in_order(k, c.x, c.y, xm0, yp.x, ym.x, zp.x, zm.x);
+                        q1 = stencil_sum_in_order(k, c.y, xp1, c.x, yp.y, ym.y, zp.y, zm.y);
                     }
-                    div_hh_mm(k, q);
+                };
+                auto row_finish = [&](const double om, const double2 c, const double q0, const double q1, const double2 fv) {
+                    const double a0 = op_finish<MODE>(k, q0, c.x, 0.0);
+                    const double a1 = op_finish<MODE>(k, q1, c.y, 0.0);
+                    return make_double2(jacobi_update<MODE>(k, c.x, fv.x - a0, 0.0, om),
+                                        jacobi_update<MODE>(k, c.y, fv.y - a1, 0.0, om));
+                };
+                auto kept = [&](const bool keep, const double2 c, const double2 n) {
+                    return make_double2((keep || bx0) ? c.x : n.x, (keep || bx1) ? c.y : n.y);
+                };
+                // ---- the three sweeps; wave 1 (mirrored rows) runs its own copy of the code. The keep selects run only
+                // where some row, column or the plane is a boundary (a wave-uniform branch)
+                // sweep 1 at plane z+1 (a lagging wave: at plane z), sweep 2 at plane z-1; F1: f at plane z-1 as sweep 2
+                // read it (-> f2_l)
+                double2 S1n[N0], S2n[N1], F1[N1];
+                const bool pz0 = planeok(LAG ? z : z + 1), pz1 = planeok(z - 1);
+                static_assert(N0 % B1 == 0 && N1 % B2 == 0 && RY % B3 == 0, "whole division batches");
+                // sweep 1 at plane z+1 (z), local rows -1..RY, into S1o
+                auto sweep1 = [&](auto mirc, double2(&S1o)[N0]) {
+                    if constexpr (YL) vY = YR[0][lane];
 #pragma unroll
-                    for (int i = b; i < b + B2; i++)
-                        S2n[i] = row_finish(k.omega[1], S1c[i + 1], q[2 * (i - b)], q[2 * (i - b) + 1], F1[i]);
-                }
-                if (!FX || !pz1 || !in2) {
+                    for (int b = 0; b < N0; b += B1) {
+                        double q[2 * B1];
 #pragma unroll
-                    for (int i = 0; i < N1; i++) S2n[i] = kept(!pz1 || !rowc[i + 2], S1c[i + 1], S2n[i]);
-                }
-            };
-            // sweep 3 at plane z-2, own rows 1..RY
-            auto sweep3 = [&](auto mirc) {
-                if (z - 2 >= zb && z - 2 <= ze) {
-                    const int64_t zo = (int64_t)(z - 2) * ldz;
+                        for (int i = b; i < b + B1; i++)
+#ifdef GS_EXP_T3_FLIGHT
+                            row_sums(mirc, Vc[i], i == 0 ? Vc[1] : Vc[i - 1], i == N0 - 1 ? vY : Vc[i + 1], Vp[i], Vp[i],
+                                     CL[i], CR[i], q[2 * (i - b)], q[2 * (i - b) + 1]);
+#else
+                            row_sums(mirc, Vc[i], i == 0 ? HL[cs] : Vc[i - 1], i == N0 - 1 ? vY : Vc[i + 1], Vp[i], VL[cs][i],
+                                     CL[i], CR[i], q[2 * (i - b)], q[2 * (i - b) + 1]);
+#endif
+                        div_hh_mm(k, q);
 #pragma unroll
-                    for (int b = 1; b <= RY; b += B3) {
-                        double q[2 * B3];
-                        double2 fv[B3];
+                        for (int i = b; i < b + B1; i++)
+#ifdef GS_EXP_T3_FLIGHT
+                            S1o[i] = row_finish(k.omega[0], Vc[i], q[2 * (i - b)], q[2 * (i - b) + 1], Vp[i]);
+#else
+                            S1o[i] = row_finish(k.omega[0], Vc[i], q[2 * (i - b)], q[2 * (i - b) + 1], FL[cs][i]);
+#endif
+                    }
+                    if (!FX || !pz0 || !in1) {
 #pragma unroll
-                        for (int j = b; j < b + B3; j++) {
-                            fv[j - b] = RS ? F2[j - 1] : f2_l[j - 1][wid][lane];
-                            row_sums(mirc, S2c[j], S2c[j - 1], j == RY ? s2Y : S2c[j + 1],
-                                     RS ? S2p[j - 1] : s2p_l[j - 1][wid][lane],
-                                     GS_T3_ZP(S2n[j], S2c[j]), CL[N0 + N1 + j - 1], CR[N0 + N1 + j - 1], q[2 * (j - b)],
-                                     q[2 * (j - b) + 1]);
+                        for (int i = 0; i < N0; i++) S1o[i] = kept(!pz0 || !rowc[i + 1], Vc[i], S1o[i]);
+                    }
+                };
+                // sweep 2 at plane z-1, local rows 0..RY; a lagging wave takes its z+ operand from the sweep 1 it has just
+                // run, and f(z-1) from the slot that sweep 1 wrote one step ago
+                auto sweep2 = [&](auto mirc) {
+                    if constexpr (YL) s1Y = YR[1][lane];
+#pragma unroll
+                    for (int b = 0; b < N1; b += B2) {
+                        double q[2 * B2];
+#pragma unroll
+                        for (int i = b; i < b + B2; i++) {
+                            F1[i] = f1_l[LAG ? cs : ph][i][wid][lane];
+                            row_sums(mirc, S1c[i + 1], S1c[i], i == N1 - 1 ? s1Y : S1c[i + 2],
+                                     RS ? S1p[i] : s1p_l[i][wid][lane],
+                                     GS_T3_ZP(S1a[i + 1], S1c[i + 1]),
+                                     CL[N0 + i], CR[N0 + i], q[2 * (i - b)], q[2 * (i - b) + 1]);
                         }
                         div_hh_mm(k, q);
 #pragma unroll
-                        for (int j = b; j < b + B3; j++) {
-                            const double2 o = row_finish(k.omega[2], S2c[j], q[2 * (j - b)], q[2 * (j - b) + 1], fv[j - b]);
-                            if (yof(j) <= ny) {
-                                if constexpr (SA) {
-                                    xo = sa_lane(xo); // (redefined in the store's own block: sa_base above)
-                                    const uint64_t qb = sa_base(out + roff[j + 2] + zo);
-                                    if (okx1) sa_st2nt(qb, xo, o.x, o.y);
-                                    else if (okx0) sa_st1(qb, xo, o.x);
-                                } else {
-                                    double* qo = out + x + roff[j + 2] + zo;
-                                    if (okx1) st2s<true>(qo, o.x, o.y);
-                                    else if (okx0) *qo = o.x;
+                        for (int i = b; i < b + B2; i++)
+                            S2n[i] = row_finish(k.omega[1], S1c[i + 1], q[2 * (i - b)], q[2 * (i - b) + 1], F1[i]);
+                    }
+                    if (!FX || !pz1 || !in2) {
+#pragma unroll
+                        for (int i = 0; i < N1; i++) S2n[i] = kept(!pz1 || !rowc[i + 2], S1c[i + 1], S2n[i]);
+                    }
+                };
+                // sweep 3 at plane z-2, own rows 1..RY
+                auto sweep3 = [&](auto mirc) {
+                    if (z - 2 >= zb && z - 2 <= ze) {
+                        if constexpr (YL) s2Y = YR[2][lane];
+                        const int64_t zo = (int64_t)(z - 2) * ldz;
+#pragma unroll
+                        for (int b = 1; b <= RY; b += B3) {
+                            double q[2 * B3];
+                            double2 fv[B3];
+#pragma unroll
+                            for (int j = b; j < b + B3; j++) {
+                                fv[j - b] = RS ? F2[j - 1] : f2_l[j - 1][wid][lane];
+                                row_sums(mirc, S2c[j], S2c[j - 1], j == RY ? s2Y : S2c[j + 1],
+                                         RS ? S2p[j - 1] : s2p_l[j - 1][wid][lane],
+                                         GS_T3_ZP(S2n[j], S2c[j]), CL[N0 + N1 + j - 1], CR[N0 + N1 + j - 1], q[2 * (j - b)],
+                                         q[2 * (j - b) + 1]);
+                            }
+                            div_hh_mm(k, q);
+#pragma unroll
+                            for (int j = b; j < b + B3; j++) {
+                                const double2 o = row_finish(k.omega[2], S2c[j], q[2 * (j - b)], q[2 * (j - b) + 1], fv[j - b]);
+                                if (yof(j) <= ny) {
+                                    if constexpr (SA) {
+                                        xo = sa_lane(xo); // (redefined in the store's own block: sa_base above)
+                                        const uint64_t qb = sa_base(out + roff[j + 2] + zo);
+                                        if (okx1) sa_st2nt(qb, xo, o.x, o.y);
+                                        else if (okx0) sa_st1(qb, xo, o.x);
+                                    } else {
+                                        double* qo = out + x + roff[j + 2] + zo;
+                                        if (okx1) st2s<true>(qo, o.x, o.y);
+                                        else if (okx0) *qo = o.x;
+                                    }
                                 }
                             }
                         }
                     }
-                }
-            };
-            if (mir) sweep2(BoolC<true>{}), sweep3(BoolC<true>{});
-            else sweep2(BoolC<false>{}), sweep3(BoolC<false>{});
-            // ---- rotate the state of sweeps 2 and 3 (each lane's LDS rows are read by this lane alone) ...
+                };
+                // ---- rotate the state of sweeps 2 and 3 (each lane's LDS rows are read by this lane alone) ...
+                auto rotate23 = [&] {
 #pragma unroll
-            for (int j = 1; j <= RY; j++) {
-                if constexpr (RS) {
-                    S2p[j - 1] = S2c[j];
-                    F2[j - 1] = F1[j];
+                    for (int j = 1; j <= RY; j++) {
+                        if constexpr (RS) {
+                            S2p[j - 1] = S2c[j];
+                            F2[j - 1] = F1[j];
+                        } else {
+                            s2p_l[j - 1][wid][lane] = S2c[j];
+                            f2_l[j - 1][wid][lane] = F1[j];
+                        }
+                    }
+#pragma unroll
+                    for (int i = 0; i < N1; i++) {
+                        S2c[i] = S2n[i];
+                        if constexpr (RS) S1p[i] = S1c[i + 1];
+                        else s1p_l[i][wid][lane] = S1c[i + 1];
+                    }
+#pragma unroll
+                    for (int i = 0; i < N0; i++) S1c[i] = S1a[i];
+                };
+                // ---- ... and of sweep 1: f into the slot sweep 2 reads, v one plane on
+                auto rotate1 = [&] {
+#pragma unroll
+                    for (int i = 0; i < N1; i++) f1_l[ph][i][wid][lane] = FL[cs][i + 1];
+#pragma unroll
+                    for (int i = 0; i < N0; i++) {
+                        Vp[i] = Vc[i];
+                        Vc[i] = VL[cs][i];
+                    }
+                };
+                if constexpr (LAG) {
+                    // the lagging half: sweep 1 first (the plane the leading half evaluated at the end of the previous
+                    // step; its result is sweep 2's z+ operand at once), then the loads into the slot it has just
+                    // consumed, then sweeps 2 and 3
+                    sweep1(BoolC<true>{}, S1a);
+                    rotate1();
+                    load_slot(cs, cz(z + 2), cz(z + 3));
+                    sweep2(BoolC<true>{}), sweep3(BoolC<true>{});
+                    rotate23();
                 } else {
-                    s2p_l[j - 1][wid][lane] = S2c[j];
-                    f2_l[j - 1][wid][lane] = F1[j];
+                    if (mir) sweep2(BoolC<true>{}), sweep3(BoolC<true>{});
+                    else sweep2(BoolC<false>{}), sweep3(BoolC<false>{});
+                    rotate23();
+                    // sweep 1 last: it reads only v and f, the second, independent chain of the step
+                    if (mir) sweep1(BoolC<true>{}, S1n);
+                    else sweep1(BoolC<false>{}, S1n);
+#pragma unroll
+                    for (int i = 0; i < N0; i++) S1a[i] = S1n[i];
+                    rotate1();
                 }
-            }
-#pragma unroll
-            for (int i = 0; i < N1; i++) {
-                S2c[i] = S2n[i];
-                if constexpr (RS) S1p[i] = S1c[i + 1];
-                else s1p_l[i][wid][lane] = S1c[i + 1];
-            }
-#pragma unroll
-            for (int i = 0; i < N0; i++) S1c[i] = S1a[i];
-            // ---- ... then sweep 1, which reads only v and f: the second, independent chain of the step
-            if (mir) sweep1(BoolC<true>{});
-            else sweep1(BoolC<false>{});
-#pragma unroll
-            for (int i = 0; i < N1; i++) f1_l[ph][i][wid][lane] = FL[cs][i + 1];
-#pragma unroll
-            for (int i = 0; i < N0; i++) {
-                S1a[i] = S1n[i];
-                Vp[i] = Vc[i];
-                Vc[i] = VL[cs][i];
             }
         }
+    };
+    if constexpr (ST) {
+        if (wy != 0) half(BoolC<true>{});
+        else half(BoolC<false>{});
+    } else {
+        half(BoolC<false>{});
     }
 }
 

@@ -753,8 +753,9 @@ const char* gs_strerror(int code)
 
 const char* gs_build_info(void)
 {
-    return "gpusolve_hip v17: LINEAR triples k_tb3y(the pair's whole-row tile, three sweeps per pass, sweep 1 one plane "
-           "ahead and last in the step, two load slots, scalar row bases + 32-bit lane offsets, "
+    return "gpusolve_hip v18: LINEAR triples k_tb3y(the pair's whole-row tile, three sweeps per pass, sweep 1 one plane "
+           "ahead and last in the step, whole-wave rows: the mirrored y-waves half a step behind (sweep 1 first, own z "
+           "loop, s_setprio 1), two load slots, scalar row bases + 32-bit lane offsets, "
            "previous-plane rows in registers, per-lane f in LDS, x-edge values read row by row from LDS into the DPP "
            "shift), "
            "pairs k_tb2y(4x2 waves, 2 rows/wave, one round of z-chunks on large levels, LINEAR 2-step prefetch; +prolong; "
