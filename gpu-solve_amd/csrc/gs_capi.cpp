@@ -116,6 +116,39 @@ void* gs_grid_create(const gs_params* p)
     }
 }
 
+void* gs_grid_create_coarsen(const gs_params* p, int coarsen)
+{
+    if (!p) {
+        g_err = "null params";
+        return nullptr;
+    }
+    try {
+        if (coarsen != GS_COARSEN_XYZ && coarsen != GS_COARSEN_XY)
+            throw gs::Error("coarsen: the value must be GS_COARSEN_XYZ (0) or GS_COARSEN_XY (1)");
+        auto* h = new Handle;
+        h->grid = std::make_unique<gs::HipGridData>(toParams(p), nullptr, -1, nullptr, coarsen);
+        return h;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return nullptr;
+    }
+}
+
+int gs_grid_get_coarsen(void* grid) { return G(grid).coarsen; }
+
+int gs_grid_level_stencil(void* grid, int level, gs_stencil* out)
+{
+    if (level < 0 || level >= (int)G(grid).numLevels() || !out) return 1;
+    *out = G(grid).getLevel(level).sten;
+    return 0;
+}
+
+int gs_grid_level_smoother(void* grid, int level)
+{
+    if (level < 0 || level >= (int)G(grid).numLevels()) return -1;
+    return G(grid).getLevel(level).line ? 1 : 0;
+}
+
 void gs_grid_destroy(void* grid)
 {
     auto* h = static_cast<Handle*>(grid);

@@ -168,23 +168,48 @@ static const char* const kTransferSingleGpu =
 // Level hierarchy: L = floor(log2(min dim)) + 1, dims halve per level, h_l = 1/(ny_l+1)
 // (src/cpu/CpuGridData.cpp:19-41). Fields a mode never touches are not allocated.
 HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomeratePoints,
-                         std::vector<std::string>* traceLog)
+                         std::vector<std::string>* traceLog, int coarsenArg)
     : GridParams(grid), trace(traceLog), comm_(comm), stream_(traceLog == nullptr),
       // the exchange path at high priority: when the interior sweep's blocks retire, the dispatcher
       // hands the freed CUs to the boundary planes and the ghost exchange first
       commStream_(traceLog == nullptr, true), bndStream_(traceLog == nullptr && comm != nullptr && comm->size() > 1, true)
 {
     const bool dry = traceLog != nullptr;
-    const std::size_t mn = std::min(std::min(gridDim[0], gridDim[1]), gridDim[2]);
-    if (mn == 0) throw Error("grid dimensions must be positive");
-    const int nlev = (int)std::floor(std::log((double)mn) / std::log(2.0)) + 1;
-    levels_.resize(nlev);
+    if (std::min(std::min(gridDim[0], gridDim[1]), gridDim[2]) == 0) throw Error("grid dimensions must be positive");
     for (int i = 0; i < 7; i++) {
         stencilAbi.s[i] = stencil.values[i];
         stencilAbi.ox[i] = stencil.getXOffset(i);
         stencilAbi.oy[i] = stencil.getYOffset(i);
         stencilAbi.oz[i] = stencil.getZOffset(i);
     }
+    // GS_COARSEN=xy|xyz: the coarsening where the caller leaves it open; anything else, and XY on a grid that cannot
+    // take it, throws here, before any work or collective
+    coarsen = coarsenArg;
+    if (coarsen < 0) {
+        coarsen = 0;
+        if (const char* e = std::getenv("GS_COARSEN")) {
+            const std::string t = e;
+            if (t == "xy") coarsen = 1;
+            else if (t != "xyz")
+                throw Error("GS_COARSEN=" + t + ": the value must be xy or xyz");
+        }
+    }
+    if (coarsen != 0 && coarsen != 1) throw Error("coarsen: the value must be GS_COARSEN_XYZ (0) or GS_COARSEN_XY (1)");
+    if (xy()) {
+        gs_stencil t;
+        if (mode != LINEAR)
+            throw Error("coarsen: XY needs a LINEAR grid (NONLINEAR and NEWTON semi-coarsening are not built)");
+        if (nranks() > 1 || traceLog)
+            throw Error("coarsen: XY needs a single-GPU grid (not a Z-slab / RCCL or schedule-trace grid: every level "
+                        "keeps all planes)");
+        if (gs_semi_level_stencil(&stencilAbi, 1.0, 1.0, &t) != 0)
+            throw Error("coarsen: XY needs a stencil of the seven axis offsets, once each (the level stencils "
+                        "re-discretise its x / y part)");
+        if (std::min(gridDim[0], gridDim[1]) < 2) throw Error("coarsen: XY needs at least 2 points in x and in y");
+    }
+    const std::size_t mn = xy() ? std::min(gridDim[0], gridDim[1]) : std::min(std::min(gridDim[0], gridDim[1]), gridDim[2]);
+    const int nlev = (int)std::floor(std::log((double)mn) / std::log(2.0)) + 1;
+    levels_.resize(nlev);
     {
         auto on = [](const char* name) { return std::getenv(name) != nullptr; };
         sw.fusedSweeps = !on("GS_NO_FUSED_SWEEPS");
@@ -228,10 +253,12 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
     if (const char* e = std::getenv("GS_SMOOTHER")) {
         const std::string t = e;
         if (t == "zline") smootherEnv = 1;
+        else if (t == "auto") smootherEnv = 2;
         else if (t != "jacobi")
-            throw Error("GS_SMOOTHER=" + t + ": the value must be zline or jacobi");
+            throw Error("GS_SMOOTHER=" + t + ": the value must be zline, auto or jacobi");
     }
     if (smootherEnv == 1) zlineCheck();
+    if (smootherEnv == 2) zlineCheck("AUTO");
     // GS_FMG_PROLONG=position|aligned: full multigrid's prolongation (setFmgProlong, once the levels exist)
     int fmgProlongEnv = 0;
     if (const char* e = std::getenv("GS_FMG_PROLONG")) {
@@ -245,7 +272,7 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
         LevelData& L = levels_[l];
         L.levelDim = l == 0 ? gridDim
                             : std::array<std::size_t, 3>{levels_[l - 1].levelDim[0] / 2, levels_[l - 1].levelDim[1] / 2,
-                                                         levels_[l - 1].levelDim[2] / 2};
+                                                         xy() ? levels_[l - 1].levelDim[2] : levels_[l - 1].levelDim[2] / 2};
         nzs.push_back((int64_t)L.levelDim[2]);
         pts.push_back((int64_t)(L.levelDim[0] * L.levelDim[1] * L.levelDim[2]));
     }
@@ -281,8 +308,10 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
         if (mode == NEWTON && sw.newtonB && dry) L.bfac = DeviceField(nx, ny, nz, s, dry); // (else: below)
         if (mode == NEWTON && l == 1 && nlev >= 3 && !L.distributed) L.newtonVNext = DeviceField(nx, ny, nz, s, dry);
         L.geom = gs_level{nx, ny, nz, L.v.ldy(), L.v.ldz(), L.lo - 1, L.h};
-        maxParts = std::max(maxParts, gs_residual_num_partials(&stencilAbi, &L.geom));
-        maxParts = std::max(maxParts, gs_jacobi_sweep2_num_partials(&stencilAbi, &L.geom, (int)mode));
+        L.sten = stencilAbi;
+        if (xy()) check(gs_semi_level_stencil(&stencilAbi, levels_[0].h, L.h, &L.sten), "gs_semi_level_stencil");
+        maxParts = std::max(maxParts, gs_residual_num_partials(&L.sten, &L.geom));
+        maxParts = std::max(maxParts, gs_jacobi_sweep2_num_partials(&L.sten, &L.geom, (int)mode));
         L.minPlanes = nz;
         if (L.distributed)
             for (int q = 0; q < nranks(); q++) L.minPlanes = std::min(L.minPlanes, L.ranksHi[q] - L.ranksLo[q] + 1);
@@ -290,12 +319,13 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
         // on the thinnest slab, as the kernel's fill count grows with the plane count
         gs_level thin = L.geom;
         thin.nz = L.minPlanes;
-        L.fusedPairs = sw.fusedSweeps && gs_jacobi_sweep2_supported_mode(&stencilAbi, &thin, (int)mode) == 2 &&
+        L.fusedPairs = sw.fusedSweeps && gs_jacobi_sweep2_supported_mode(&L.sten, &thin, (int)mode) == 2 &&
                        (!L.distributed || L.minPlanes >= 2);
         L.fusedTriples = sw.sweep3 && sw.fusedSweeps && mode == LINEAR && !L.distributed && pts[l] >= sw.sweep3MinPoints &&
-                         gs_jacobi_sweep3_supported(&stencilAbi, &L.geom) == 2;
-        L.tiled = !L.distributed && pts[l] <= sw.tilePoints &&
-                  gs_tiled_supported(&stencilAbi, &L.geom, (int)mode) != 0;
+                         gs_jacobi_sweep3_supported(&L.sten, &L.geom) == 2;
+        // (the tiled steps embed the 3-D transfers: not on an XY hierarchy)
+        L.tiled = !xy() && !L.distributed && pts[l] <= sw.tilePoints &&
+                  gs_tiled_supported(&L.sten, &L.geom, (int)mode) != 0;
     }
     // The coarse end of the V-cycle runs as one gs_coarse_cycle launch from the first level of at
     // most GS_COARSE_POINTS points that is not Z-slab partitioned; 0 = off. Default 512 = 8^3: a 16^3
@@ -305,7 +335,7 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
     {
         const char* e = std::getenv("GS_COARSE_POINTS");
         const int64_t thr = e ? std::atoll(e) : 512;
-        if (thr > 0 && preSmoothing + postSmoothing < (1u << 20))
+        if (thr > 0 && preSmoothing + postSmoothing < (1u << 20) && !xy()) // (XY: one stencil per level, 2-D transfers)
             for (int l = nlev - 1; l >= 1; l--) {
                 if (levels_[l].distributed || pts[l] > thr || nlev - l > gs_coarse_cycle_max_levels()) break;
                 coarseFrom = (std::size_t)l;
@@ -378,6 +408,7 @@ HipGridData::HipGridData(const GridParams& grid, Comm* comm, int64_t agglomerate
         if (bndStream_.s) levels_[l].proWs[1].get(need);
     }
     check((int)hipStreamSynchronize(s), "hipStreamSynchronize");
+    if (xy()) buildXyTables();
     if (transferEnv) setTransfer(transferEnv);
     if (fmgProlongEnv) setFmgProlong(fmgProlongEnv);
     if (smootherEnv) setSmoother(smootherEnv);
@@ -387,7 +418,59 @@ bool HipGridData::levelAligned(std::size_t l) const
 {
     if (l + 1 >= levels_.size()) return true;
     const auto &f = levels_[l].levelDim, &c = levels_[l + 1].levelDim;
-    return f[0] == 2 * c[0] + 1 && f[1] == 2 * c[1] + 1 && f[2] == 2 * c[2] + 1;
+    return f[0] == 2 * c[0] + 1 && f[1] == 2 * c[1] + 1 && (xy() || f[2] == 2 * c[2] + 1);
+}
+
+// One transition's tables (gs_transfer_axis per axis) in one device allocation: per axis pt, rw, then per axis pj, rlo,
+// rcnt (the doubles first, so that every array is 8-byte aligned). axes = 3: a POSITION transition; axes = 2: a
+// transition of an XY hierarchy (axis 2: nf = nc = nz, no arrays).
+gs_transfer_tables HipGridData::uploadTransferTables(std::size_t l, int axes)
+{
+    gs_transfer_tables T{};
+    std::vector<std::vector<int32_t>> pj(axes), rlo(axes), rcnt(axes);
+    std::vector<std::vector<double>> pt(axes), rw(axes);
+    std::size_t bytes = 0;
+    for (int a = 0; a < axes; a++) {
+        const int64_t nf = (int64_t)levels_[l].levelDim[a], nc = (int64_t)levels_[l + 1].levelDim[a];
+        T.nf[a] = nf;
+        T.nc[a] = nc;
+        pj[a].resize(nf + 2);
+        pt[a].resize(nf + 2);
+        rlo[a].resize(nc + 2);
+        rcnt[a].resize(nc + 2);
+        rw[a].resize(4 * (nc + 2));
+        check(gs_transfer_axis(nf, nc, pj[a].data(), pt[a].data(), rlo[a].data(), rcnt[a].data(), rw[a].data()),
+              "gs_transfer_axis");
+        bytes += sizeof(double) * (pt[a].size() + rw[a].size()) +
+                 sizeof(int32_t) * (pj[a].size() + rlo[a].size() + rcnt[a].size() + 2);
+    }
+    if (axes == 2) T.nf[2] = T.nc[2] = (int64_t)levels_[l].levelDim[2];
+    char* base = nullptr;
+    check((int)hipMalloc((void**)&base, bytes), "hipMalloc(transfer tables)");
+    xferMem_.push_back(base);
+    std::size_t off = 0;
+    auto put = [&](const void* src, std::size_t n) {
+        check((int)hipMemcpy(base + off, src, n, hipMemcpyHostToDevice), "hipMemcpy(transfer tables)");
+        const void* p = base + off;
+        off += n;
+        return p;
+    };
+    for (int a = 0; a < axes; a++) {
+        T.pt[a] = (const double*)put(pt[a].data(), sizeof(double) * pt[a].size());
+        T.rw[a] = (const double*)put(rw[a].data(), sizeof(double) * rw[a].size());
+    }
+    for (int a = 0; a < axes; a++) {
+        T.pj[a] = (const int32_t*)put(pj[a].data(), sizeof(int32_t) * pj[a].size());
+        T.rlo[a] = (const int32_t*)put(rlo[a].data(), sizeof(int32_t) * rlo[a].size());
+        T.rcnt[a] = (const int32_t*)put(rcnt[a].data(), sizeof(int32_t) * rcnt[a].size());
+    }
+    return T;
+}
+
+// The x / y tables of every transition of an XY hierarchy: at creation, once.
+void HipGridData::buildXyTables()
+{
+    for (std::size_t l = 0; l + 1 < levels_.size(); l++) xferT_[l] = uploadTransferTables(l, 2);
 }
 
 void HipGridData::setTransfer(int m)
@@ -398,46 +481,7 @@ void HipGridData::setTransfer(int m)
     const std::size_t nl = levels_.size();
     for (std::size_t l = 0; m == 1 && l + 1 < nl; l++) {
         if (levelAligned(l) || xferT_[l].pj[0]) continue;
-        // one allocation per transition: per axis pj, pt (nf + 2), rlo, rcnt (nc + 2), rw (4 (nc + 2)); the doubles
-        // first, so that every array is 8-byte aligned
-        gs_transfer_tables T{};
-        std::vector<std::vector<int32_t>> pj(3), rlo(3), rcnt(3);
-        std::vector<std::vector<double>> pt(3), rw(3);
-        std::size_t bytes = 0;
-        for (int a = 0; a < 3; a++) {
-            const int64_t nf = (int64_t)levels_[l].levelDim[a], nc = (int64_t)levels_[l + 1].levelDim[a];
-            T.nf[a] = nf;
-            T.nc[a] = nc;
-            pj[a].resize(nf + 2);
-            pt[a].resize(nf + 2);
-            rlo[a].resize(nc + 2);
-            rcnt[a].resize(nc + 2);
-            rw[a].resize(4 * (nc + 2));
-            check(gs_transfer_axis(nf, nc, pj[a].data(), pt[a].data(), rlo[a].data(), rcnt[a].data(), rw[a].data()),
-                  "gs_transfer_axis");
-            bytes += sizeof(double) * (pt[a].size() + rw[a].size()) +
-                     sizeof(int32_t) * (pj[a].size() + rlo[a].size() + rcnt[a].size() + 2);
-        }
-        char* base = nullptr;
-        check((int)hipMalloc((void**)&base, bytes), "hipMalloc(transfer tables)");
-        xferMem_.push_back(base);
-        std::size_t off = 0;
-        auto put = [&](const void* src, std::size_t n) {
-            check((int)hipMemcpy(base + off, src, n, hipMemcpyHostToDevice), "hipMemcpy(transfer tables)");
-            const void* p = base + off;
-            off += n;
-            return p;
-        };
-        for (int a = 0; a < 3; a++) {
-            T.pt[a] = (const double*)put(pt[a].data(), sizeof(double) * pt[a].size());
-            T.rw[a] = (const double*)put(rw[a].data(), sizeof(double) * rw[a].size());
-        }
-        for (int a = 0; a < 3; a++) {
-            T.pj[a] = (const int32_t*)put(pj[a].data(), sizeof(int32_t) * pj[a].size());
-            T.rlo[a] = (const int32_t*)put(rlo[a].data(), sizeof(int32_t) * rlo[a].size());
-            T.rcnt[a] = (const int32_t*)put(rcnt[a].data(), sizeof(int32_t) * rcnt[a].size());
-        }
-        xferT_[l] = T;
+        xferT_[l] = uploadTransferTables(l, 3);
     }
     transferMode = m;
     updateCoarseFrom();
@@ -455,48 +499,80 @@ void HipGridData::updateCoarseFrom()
         while (c > coarseFromRef_ && levelAligned(c - 1)) c--;
         coarseFrom = c;
     }
-    if (zline()) coarseFrom = nl;
+    if (anyLine || xy()) coarseFrom = nl;
 }
 
-void HipGridData::zlineCheck() const
+static const char* const kZlineStencil =
+    " needs a stencil of the seven axis offsets, once each, whose centre weight s0 is "
+    "not 0 and has |s0| >= |weight at (0,0,+1)| + |weight at (0,0,-1)|";
+
+void HipGridData::zlineCheck(const char* name) const
 {
+    const std::string who = std::string("smoother: ") + name;
     if (mode != LINEAR)
-        throw Error("smoother: ZLINE needs a LINEAR grid (NONLINEAR and NEWTON line sweeps are not built: their diagonal "
-                    "is a field)");
+        throw Error(who + " needs a LINEAR grid (NONLINEAR and NEWTON line sweeps are not built: their diagonal "
+                          "is a field)");
     if (nranks() > 1 || trace)
-        throw Error("smoother: ZLINE needs a single-GPU grid (not a Z-slab / RCCL or schedule-trace grid: the lines "
-                    "cross the slabs)");
-    if (!gs_zline_supported(&stencilAbi))
-        throw Error("smoother: ZLINE needs a stencil of the seven axis offsets, once each, whose centre weight s0 is "
-                    "not 0 and has |s0| >= |weight at (0,0,+1)| + |weight at (0,0,-1)|");
+        throw Error(who + " needs a single-GPU grid (not a Z-slab / RCCL or schedule-trace grid: the lines "
+                          "cross the slabs)");
+    // (AUTO judges every level that would run line sweeps by its own stencil: setSmoother)
+    if (std::string(name) == "ZLINE" && !gs_zline_supported(&stencilAbi)) throw Error(who + kZlineStencil);
 }
 
 void HipGridData::setSmoother(int m)
 {
-    if (m != 0 && m != 1) throw Error("smoother: the mode must be GS_SMOOTHER_JACOBI (0) or GS_SMOOTHER_ZLINE (1)");
-    if (m == 1) {
-        zlineCheck();
-        if (!zlineT_[0].cp) {
-            // one allocation: per level cp, then den (nz + 2 doubles each)
-            std::vector<double> host;
-            std::vector<std::size_t> at;
-            for (const auto& L : levels_) {
-                const std::size_t n = (std::size_t)L.geom.nz + 2;
-                at.push_back(host.size());
-                host.resize(host.size() + 2 * n);
-                check(gs_zline_factors(&stencilAbi, L.geom.nz, host.data() + at.back(), host.data() + at.back() + n),
-                      "gs_zline_factors");
+    if (m < 0 || m > 2)
+        throw Error("smoother: the mode must be GS_SMOOTHER_JACOBI (0), GS_SMOOTHER_ZLINE (1) or GS_SMOOTHER_AUTO (2)");
+    const std::size_t nl = levels_.size();
+    std::vector<char> want(nl, 0);
+    if (m != 0) {
+        zlineCheck(m == 1 ? "ZLINE" : "AUTO");
+        for (std::size_t l = 0; l < nl; l++) {
+            const gs_stencil& S = levels_[l].sten;
+            if (m == 2) {
+                // (AUTO on a grid ZLINE's shape test would refuse: no weight counts as a z weight twice; a stencil
+                // with a diagonal offset has its level refused below only if the rule picks lines for it)
+                double mz = 0.0, mxy = 0.0;
+                for (int i = 0; i < 7; i++) {
+                    if (S.ox[i] == 0 && S.oy[i] == 0 && S.oz[i] != 0) mz = std::max(mz, std::fabs(S.s[i]));
+                    else if (S.ox[i] != 0 || S.oy[i] != 0) mxy = std::max(mxy, std::fabs(S.s[i]));
+                }
+                want[l] = mz > mxy;
+            } else {
+                want[l] = 1;
             }
+            if (want[l] && !gs_zline_supported(&S))
+                throw Error(std::string("smoother: ") + (m == 1 ? "ZLINE" : "AUTO") + kZlineStencil + " (level " +
+                            std::to_string(l) + ")");
+        }
+        // one allocation for the line levels that have no factors yet: per level cp, then den (nz + 2 doubles each)
+        std::vector<double> host;
+        std::vector<std::size_t> at(nl, 0);
+        for (std::size_t l = 0; l < nl; l++) {
+            if (!want[l] || zlineT_[l].cp) continue;
+            const auto& L = levels_[l];
+            const std::size_t n = (std::size_t)L.geom.nz + 2;
+            at[l] = host.size();
+            host.resize(host.size() + 2 * n);
+            check(gs_zline_factors(&L.sten, L.geom.nz, host.data() + at[l], host.data() + at[l] + n), "gs_zline_factors");
+        }
+        if (!host.empty()) {
             double* base = nullptr;
             check((int)hipMalloc((void**)&base, sizeof(double) * host.size()), "hipMalloc(z-line factors)");
             xferMem_.push_back(base);
             check((int)hipMemcpy(base, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice),
                   "hipMemcpy(z-line factors)");
-            for (std::size_t l = 0; l < levels_.size(); l++) {
+            for (std::size_t l = 0; l < nl; l++) {
+                if (!want[l] || zlineT_[l].cp) continue;
                 const int64_t nz = levels_[l].geom.nz;
                 zlineT_[l] = gs_zline_tables{base + at[l], base + at[l] + nz + 2, nz};
             }
         }
+    }
+    anyLine = false;
+    for (std::size_t l = 0; l < nl; l++) {
+        levels_[l].line = want[l] != 0;
+        anyLine = anyLine || levels_[l].line;
     }
     smootherMode = m;
     updateCoarseFrom();
@@ -512,7 +588,7 @@ void HipGridData::setFmgProlong(int m)
 
 void HipGridData::buildFmgTables()
 {
-    if (mode == NEWTON || nranks() > 1 || trace) return; // FMG is refused there: no table is ever read
+    if (mode == NEWTON || nranks() > 1 || trace || xy()) return; // FMG is refused there: no table is ever read
     for (std::size_t l = 0; l + 1 < levels_.size(); l++) {
         if (levelAligned(l) || fmgT_[l].cj[0]) continue;
         // one allocation per transition: per axis cw (4 (nf + 2) doubles), then per axis cj (nf + 2)
@@ -805,12 +881,12 @@ int64_t sweepPlanes(HipGridData& g, HipGridData::LevelData& L, int64_t z1, int64
         g.rec("sweep", {{"L", (long long)g.levelIndex(L)}, {"z1", z1}, {"z2", z2}, {"vzero", L.vZero}, {"norm", partials != nullptr}});
         return partials ? 1 : 0;
     }
-    check(gs_jacobi_sweep_norm(&g.stencilAbi, &sub, g.kmode(), w ? w[0] : g.omega, g.gamma,
+    check(gs_jacobi_sweep_norm(&L.sten, &sub, g.kmode(), w ? w[0] : g.omega, g.gamma,
                                L.vZero ? nullptr : L.v.data() + off,
                                L.vAlt.data() + off, L.f.data() + off, g.wOf(L) ? g.wOf(L) + off : nullptr,
                                partials, s),
           "gs_jacobi_sweep");
-    return partials ? gs_residual_num_partials(&g.stencilAbi, &sub) : 0;
+    return partials ? gs_residual_num_partials(&L.sten, &sub) : 0;
 }
 
 // two fused sweeps over local planes [z1, z2]: reads L.v (two ghost planes deep where a side is an
@@ -834,18 +910,18 @@ int64_t pairPlanes(HipGridData& g, HipGridData::LevelData& L, int64_t z1, int64_
         return partials ? 1 : 0;
     }
     const double om[2] = {w ? w[0] : g.omega, w ? w[1] : g.omega};
-    check(gs_jacobi_sweep2_norm_w(&g.stencilAbi, &sub, g.kmode(), om, g.gamma, L.vZero ? nullptr : L.v.data() + off,
+    check(gs_jacobi_sweep2_norm_w(&L.sten, &sub, g.kmode(), om, g.gamma, L.vZero ? nullptr : L.v.data() + off,
                                   L.vAlt.data() + off, L.f.data() + off, g.wOf(L) ? g.wOf(L) + off : nullptr,
                                   zlo, zhi, partials, s),
           "gs_jacobi_sweep2");
-    return partials ? gs_jacobi_sweep2_num_partials(&g.stencilAbi, &sub, (int)g.mode) : 0;
+    return partials ? gs_jacobi_sweep2_num_partials(&L.sten, &sub, (int)g.mode) : 0;
 }
 
 // three fused LINEAR sweeps over a whole non-distributed level (gs_jacobi_sweep3): reads L.v, writes L.vAlt
 void tripleLevel(HipGridData& g, HipGridData::LevelData& L, hipStream_t s, const double* w)
 {
     const double om[3] = {w ? w[0] : g.omega, w ? w[1] : g.omega, w ? w[2] : g.omega};
-    check(gs_jacobi_sweep3_w(&g.stencilAbi, &L.geom, om, g.gamma, L.v.data(), L.vAlt.data(), L.f.data(), s),
+    check(gs_jacobi_sweep3_w(&L.sten, &L.geom, om, g.gamma, L.v.data(), L.vAlt.data(), L.f.data(), s),
           "gs_jacobi_sweep3");
 }
 
@@ -870,7 +946,7 @@ void proPlanes(HipGridData& g, HipGridData::LevelData& F, HipGridData::LevelData
     }
     // rows > 512 points (column blocks): the corrected edge columns go through a workspace, one per
     // stream (the boundary planes' launch runs beside the interior's)
-    const int64_t wsn = gs_jacobi_sweep2_prolong_ws_elems(&g.stencilAbi, &sub, (int)g.mode);
+    const int64_t wsn = gs_jacobi_sweep2_prolong_ws_elems(&F.sten, &sub, (int)g.mode);
     // (allocated once, at grid creation, for the largest plane range upLeg requests: never reallocated —
     // a hipFree / hipMalloc here would synchronise the device inside the overlapped sequence)
     DeviceBuf& wb = F.proWs[s == g.stream() ? 0 : 1];
@@ -879,7 +955,7 @@ void proPlanes(HipGridData& g, HipGridData::LevelData& F, HipGridData::LevelData
     // (the prolongation pair is the first two post-smoothing sweeps: post[0..1] of the per-sweep weights)
     const double* w = g.wPost();
     const double om[2] = {w ? w[0] : g.omega, w ? w[1] : g.omega};
-    check(gs_jacobi_sweep2_prolong_ws_w(&g.stencilAbi, &sub, g.kmode(), om, g.gamma, F.v.data() + off,
+    check(gs_jacobi_sweep2_prolong_ws_w(&F.sten, &sub, g.kmode(), om, g.gamma, F.v.data() + off,
                                         C.v.data(), nullptr, &C.geom, F.vAlt.data() + off, F.f.data() + off,
                                         g.wOf(F) ? g.wOf(F) + off : nullptr, zlo, zhi, ws, wsn, s),
           "gs_jacobi_sweep2_prolong");
@@ -891,6 +967,7 @@ void proPlanes(HipGridData& g, HipGridData::LevelData& F, HipGridData::LevelData
 // (the whole level, or the boundary / interior ranges of the overlapped Z-slab sequence).
 int64_t proWsElems(const HipGridData& g, std::size_t l)
 {
+    if (g.xy()) return 0; // (the fused prolongation pair embeds the 3-D interpolation: never taken)
     const gs_level& G = g.getLevel(l).geom;
     const int64_t nz = G.nz, zt = nz % 2 == 0 ? nz - 1 : nz - 2;
     const int64_t ranges[4][2] = {{1, nz}, {1, 2}, {zt, nz}, {3, zt - 1}};
@@ -900,7 +977,7 @@ int64_t proWsElems(const HipGridData& g, std::size_t l)
         gs_level sub = G;
         sub.nz = r[1] - r[0] + 1;
         sub.z0 += r[0] - 1;
-        need = std::max(need, gs_jacobi_sweep2_prolong_ws_elems(&g.stencilAbi, &sub, (int)g.mode));
+        need = std::max(need, gs_jacobi_sweep2_prolong_ws_elems(&g.getLevel(l).sten, &sub, (int)g.mode));
     }
     return need;
 }
@@ -926,7 +1003,9 @@ void restrictTo(HipGridData& g, const DeviceField& src, std::size_t l, DeviceFie
             g.rec("restrict", {{"L", (long long)l}, {"c1", cg.z0 + 1}, {"c2", cg.z0 + cg.nz}, {"two", b != nullptr}},
                   (std::string(HipGridData::fieldName(F, src)) + ">" + HipGridData::fieldName(C, a) +
                    (b ? std::string(",") + HipGridData::fieldName(C, *b) : std::string())).c_str());
-    } else if (g.pa(l))
+    } else if (g.xy())
+        check(gs_restrict_xy(src.data(), &F.geom, a.data(), &C.geom, g.xfer(l), s), "gs_restrict_xy");
+    else if (g.pa(l))
         check(gs_restrict_pa(src.data(), &F.geom, a.data(), b ? b->data() : nullptr, &C.geom, g.xfer(l), s),
               "gs_restrict_pa");
     else if (cg.nz > 0)
@@ -977,10 +1056,10 @@ void HipSolver::settleExchange(HipGridData& grid)
     if (!grid.trace) check((int)hipEventRecord(grid.evB_, grid.commStream()), "hipEventRecord");
 }
 
-// (the speculative step is a point sweep or pair: not in ZLINE mode)
+// (the speculative step is a level-0 point sweep or pair: not where level 0 runs z-line sweeps)
 bool HipSolver::speculationEnabled(const HipGridData& grid)
 {
-    return grid.sw.speculation && grid.preSmoothing > 0 && grid.numLevels() > 1 && !grid.zline();
+    return grid.sw.speculation && grid.preSmoothing > 0 && grid.numLevels() > 1 && !grid.lineAt(0);
 }
 
 // src/cpu/CpuSolver.cpp:12-43. Every norm the loop reads (the initial one and each V-cycle's closing
@@ -1098,13 +1177,13 @@ double HipSolver::compResidual(HipGridData& grid, std::size_t l, bool storeR, bo
     if (grid.trace)
         grid.rec("residual", {{"L", (long long)l}, {"store", storeR}, {"norm", norm}});
     else
-        check(gs_residual(&grid.stencilAbi, &L.geom, grid.kmode(), grid.gamma, L.v.data(), L.f.data(),
+        check(gs_residual(&L.sten, &L.geom, grid.kmode(), grid.gamma, L.v.data(), L.f.data(),
                           grid.wOf(L), storeR ? L.r.data() : nullptr,
                           norm ? grid.partials() : nullptr, s),
               "gs_residual");
     if (storeR) grid.halo(L, L.r, s);
     if (!norm) return 0.0;
-    return finishNorm(grid, gs_residual_num_partials(&grid.stencilAbi, &L.geom));
+    return finishNorm(grid, gs_residual_num_partials(&L.sten, &L.geom));
 }
 
 // Whether level l's first post-smoothing pair can take the prolongation from level l+1 (rank-uniform:
@@ -1168,10 +1247,10 @@ void HipSolver::jacobi(HipGridData& grid, std::size_t l, std::size_t sweeps, con
 {
     auto& L = grid.getLevel(l);
     const hipStream_t s = grid.stream();
-    if (grid.zline()) {
+    if (L.line) {
         // one z-line sweep per sweep (single GPU, whole levels: setSmoother): no pairs, no triples
         for (; sweeps > 0; sweeps--) {
-            check(gs_zline_sweep(&grid.stencilAbi, &L.geom, w ? *w++ : grid.omega, L.vZero ? nullptr : L.v.data(),
+            check(gs_zline_sweep(&L.sten, &L.geom, w ? *w++ : grid.omega, L.vZero ? nullptr : L.v.data(),
                                  L.vAlt.data(), L.f.data(), grid.zlineTables(l), s),
                   "gs_zline_sweep");
             L.v.swap(L.vAlt);
@@ -1288,11 +1367,11 @@ void HipSolver::coarseCycle(HipGridData& grid, std::size_t from)
     if (grid.trace)
         grid.rec("coarse", {{"from", (long long)from}, {"vzero", lv[0].v_zero}});
     else if (grid.weighted())
-        check(gs_coarse_cycle_w(&grid.stencilAbi, lv, n, grid.kmode(), grid.wPre(), grid.gamma, (int)grid.preSmoothing,
+        check(gs_coarse_cycle_w(&grid.getLevel(from).sten, lv, n, grid.kmode(), grid.wPre(), grid.gamma, (int)grid.preSmoothing,
                                 (int)grid.postSmoothing, grid.stream()),
               "gs_coarse_cycle");
     else
-        check(gs_coarse_cycle(&grid.stencilAbi, lv, n, grid.kmode(), grid.omega, grid.gamma, (int)grid.preSmoothing,
+        check(gs_coarse_cycle(&grid.getLevel(from).sten, lv, n, grid.kmode(), grid.omega, grid.gamma, (int)grid.preSmoothing,
                               (int)grid.postSmoothing, grid.stream()),
               "gs_coarse_cycle");
     const bool odd = ((grid.preSmoothing + grid.postSmoothing) & 1) != 0; // every level swept pre+post times
@@ -1361,8 +1440,9 @@ void HipSolver::upLeg(HipGridData& grid, std::size_t i)
     materialize(grid, i); // only if the level had no sweep at all
     // (the tiled step fuses the prolongation with a pair: the GS_NO_FUSED_SWEEPS / GS_NO_FUSED_PROLONG
     // alternatives take the general path below)
-    const bool pa = grid.pa(i - 1); // position-aware transfers: the general path below, with gs_prolong_add_pa
-    const bool zl = grid.zline(); // z-line sweeps: neither fused step below, both embed point Jacobi
+    const bool xy = grid.xy(); // XY hierarchy: the general path below, with gs_prolong_add_xy
+    const bool pa = xy || grid.pa(i - 1); // position-aware transfers: the general path below, with gs_prolong_add_pa
+    const bool zl = F.line; // z-line sweeps: neither fused step below, both embed point Jacobi
     if (!pa && !zl && i - 1 >= 1 && F.tiled && !C.distributed && grid.postSmoothing >= 2 && grid.sw.fusedSweeps &&
         grid.sw.fusedProlong) {
         // a small level: prolongation, correction and the first two post-smoothing sweeps in one launch
@@ -1372,7 +1452,7 @@ void HipSolver::upLeg(HipGridData& grid, std::size_t i)
         else {
             const double* w = grid.wPost();
             const double om[2] = {w ? w[0] : grid.omega, w ? w[1] : grid.omega};
-            check(gs_prolong_smooth2_tiled_w(&grid.stencilAbi, &F.geom, grid.kmode(), om, grid.gamma, F.v.data(),
+            check(gs_prolong_smooth2_tiled_w(&F.sten, &F.geom, grid.kmode(), om, grid.gamma, F.v.data(),
                                              C.v.data(), &C.geom, F.vAlt.data(), F.f.data(), grid.wOf(F), s),
                   "gs_prolong_smooth2_tiled");
         }
@@ -1384,7 +1464,7 @@ void HipSolver::upLeg(HipGridData& grid, std::size_t i)
         return;
     }
     if (!pa && !zl && grid.sw.fusedProlong && F.fusedPairs && grid.postSmoothing >= 2 && proWorthIt(grid, i - 1) && proSlabOk(grid, i - 1) &&
-        gs_jacobi_sweep2_prolong_supported(&grid.stencilAbi, &F.geom, (int)grid.mode)) {
+        gs_jacobi_sweep2_prolong_supported(&F.sten, &F.geom, (int)grid.mode)) {
         // the first two post-smoothing sweeps of v^h + P v^2h in one pass (the corrected
         // iterate is never stored), then the remaining ones. On a Z-slab each rank corrects its
         // ghost planes itself, from the coarse planes under them, and the pair's outermost planes
@@ -1417,7 +1497,10 @@ void HipSolver::upLeg(HipGridData& grid, std::size_t i)
     // v^h += P (v^2h [- restV^2h])   (CpuSolver.cpp:121-132, interpolate + v += e fused)
     if (grid.trace)
         grid.rec("prolongadd", {{"L", (long long)(i - 1)}, {"sub", grid.mode == GridParams::NONLINEAR}});
-    else if (pa) {
+    else if (xy) {
+        materialize(grid, i - 1);
+        check(gs_prolong_add_xy(C.v.data(), &C.geom, F.v.data(), &F.geom, grid.xfer(i - 1), s), "gs_prolong_add_xy");
+    } else if (pa) {
         materialize(grid, i - 1);
         check(gs_prolong_add_pa(C.v.data(), grid.mode == GridParams::NONLINEAR ? C.restV.data() : nullptr, &C.geom,
                                 F.v.data(), &F.geom, grid.xfer(i - 1), s),
@@ -1455,8 +1538,9 @@ void HipSolver::downFrom(HipGridData& grid, std::size_t from, int* pending)
         auto& C = grid.getLevel(i + 1);
         // (the tiled step fuses a pair, the residual and the restriction and leaves v^2h = 0 as a flag: the
         // GS_NO_FUSED_SWEEPS / GS_NO_FUSED_RR / GS_NO_ZERO_GUESS alternatives take the general path below)
-        const bool pa = grid.pa(i); // position-aware transfers: the general path below with the _pa launchers
-        if (!pa && !grid.zline() && i >= 1 && pre == 2 && L.tiled && !C.distributed && grid.sw.fusedSweeps &&
+        const bool xy = grid.xy(); // XY hierarchy: the general path below with the _xy launchers
+        const bool pa = xy || grid.pa(i); // position-aware transfers: the general path below with the _pa launchers
+        if (!pa && !L.line && i >= 1 && pre == 2 && L.tiled && !C.distributed && grid.sw.fusedSweeps &&
             grid.sw.fusedRR && grid.sw.zeroGuess) {
             // a small level: the pre-smoothing pair, residual and restriction in one tiled launch
             if (grid.trace)
@@ -1464,7 +1548,7 @@ void HipSolver::downFrom(HipGridData& grid, std::size_t from, int* pending)
             else {
                 const double* w = grid.wPre(); // (i >= 1: no speculative sweeps, the pair is pre[0..1])
                 const double om[2] = {w ? w[0] : grid.omega, w ? w[1] : grid.omega};
-                check(gs_smooth2_restrict_tiled_w(&grid.stencilAbi, &L.geom, grid.kmode(), om, grid.gamma,
+                check(gs_smooth2_restrict_tiled_w(&L.sten, &L.geom, grid.kmode(), om, grid.gamma,
                                                   L.vZero ? nullptr : L.v.data(), L.vAlt.data(), L.f.data(),
                                                   grid.wOf(L), C.f.data(), &C.geom, s),
                       "gs_smooth2_restrict_tiled");
@@ -1482,9 +1566,14 @@ void HipSolver::downFrom(HipGridData& grid, std::size_t from, int* pending)
         if (grid.sw.fusedRR) {
             materialize(grid, i);
             const double* w = grid.wOf(L);
-            if (pa) {
+            if (xy) {
+                check(gs_residual_restrict_xy(&L.sten, &L.geom, L.v.data(), L.f.data(), C.f.data(), &C.geom,
+                                              grid.xfer(i), s),
+                      "gs_residual_restrict_xy");
+                fused = true;
+            } else if (pa) {
                 if (HipGridData::paFusedRR) {
-                    check(gs_residual_restrict_pa(&grid.stencilAbi, &L.geom, grid.kmode(), grid.gamma, L.v.data(),
+                    check(gs_residual_restrict_pa(&L.sten, &L.geom, grid.kmode(), grid.gamma, L.v.data(),
                                                   L.f.data(), w, C.f.data(), &C.geom, grid.xfer(i), s),
                           "gs_residual_restrict_pa");
                     fused = true;
@@ -1493,7 +1582,7 @@ void HipSolver::downFrom(HipGridData& grid, std::size_t from, int* pending)
                 if (grid.trace)
                     grid.rec("resrestrict", {{"L", (long long)i}, {"c1", 1}, {"c2", C.geom.nz}, {"zhi", 0}});
                 else
-                    check(gs_residual_restrict(&grid.stencilAbi, &L.geom, grid.kmode(), grid.gamma, L.v.data(),
+                    check(gs_residual_restrict(&L.sten, &L.geom, grid.kmode(), grid.gamma, L.v.data(),
                                                L.f.data(), w, C.f.data(), nullptr, &C.geom, s),
                           "gs_residual_restrict");
                 fused = true;
@@ -1510,12 +1599,12 @@ void HipSolver::downFrom(HipGridData& grid, std::size_t from, int* pending)
                 const int zhi = grid.rank() + 1 < grid.nranks();
                 // (the residual on the top ghost plane reads v two planes deep)
                 slabOk = slabOk && grid.vDepth(L) == 2 &&
-                         gs_residual_restrict_slab_supported(&grid.stencilAbi, &L.geom) != 0;
+                         gs_residual_restrict_slab_supported(&L.sten, &L.geom) != 0;
                 if (slabOk) {
                     if (cg.nz > 0 && grid.trace)
                         grid.rec("resrestrict", {{"L", (long long)i}, {"c1", cg.z0 + 1}, {"c2", cg.z0 + cg.nz}, {"zhi", zhi}});
                     else if (cg.nz > 0)
-                        check(gs_residual_restrict_slab(&grid.stencilAbi, &L.geom, grid.kmode(), grid.gamma,
+                        check(gs_residual_restrict_slab(&L.sten, &L.geom, grid.kmode(), grid.gamma,
                                                         L.v.data(), L.f.data(), w, C.f.data() + off, nullptr, &cg,
                                                         zhi, s),
                               "gs_residual_restrict_slab");
@@ -1543,7 +1632,7 @@ void HipSolver::downFrom(HipGridData& grid, std::size_t from, int* pending)
             if (grid.trace)
                 grid.rec("applyadd", {{"L", (long long)(i + 1)}});
             else
-                check(gs_apply_op_add(&grid.stencilAbi, &C.geom, grid.gamma, C.restV.data(), C.f.data(), s),
+                check(gs_apply_op_add(&C.sten, &C.geom, grid.gamma, C.restV.data(), C.f.data(), s),
                       "gs_apply_op_add");
             grid.halo(C, C.f, s);
         }
@@ -1569,7 +1658,7 @@ void HipSolver::vcycleFrom(HipGridData& grid, std::size_t level)
 
 std::size_t HipSolver::fmgStartLevel(const HipGridData& grid)
 {
-    if (grid.mode == GridParams::NEWTON || grid.nranks() > 1 || grid.trace) return 0;
+    if (grid.mode == GridParams::NEWTON || grid.nranks() > 1 || grid.trace || grid.xy()) return 0;
     if (grid.fmgProlongMode == 1) return grid.numLevels() - 1; // every transition can be prolonged
     std::size_t s = 0;
     while (s + 1 < grid.numLevels() && gs_fmg_prolong_supported(&grid.getLevel(s + 1).geom, &grid.getLevel(s).geom)) s++;
@@ -1582,6 +1671,9 @@ void HipSolver::fmgCheck(const HipGridData& grid, int cyclesPerLevel)
         throw Error("FMG: NEWTON mode is not supported (LINEAR and NONLINEAR grids only)");
     if (grid.nranks() > 1 || grid.trace)
         throw Error("FMG: single-GPU grids only (not a Z-slab / RCCL or schedule-trace grid)");
+    if (grid.xy())
+        throw Error("FMG: not on an XY semi-coarsened grid (gs_fmg_prolong interpolates in z too; an XY full-multigrid "
+                    "start is not built)");
     if (cyclesPerLevel < 1) throw Error("FMG: cycles per level must be at least 1");
     if (grid.fmgProlongMode == 1 && grid.transferMode == 0)
         for (std::size_t l = 0; l + 1 < grid.numLevels(); l++)
@@ -1725,7 +1817,8 @@ void HipSolver::pcgCheck(const HipGridData& grid)
     for (int o = 0; o < 27; o++)
         if (!(wgt[o] == wgt[26 - o]))
             throw Error("PCG: the stencil must be symmetric: the weight at every offset o must be the weight at -o");
-    if (grid.transferMode == 0)
+    // (an XY hierarchy's transfers are by position on every transition: R_xy is the scaled transpose of P_xy)
+    if (grid.transferMode == 0 && !grid.xy())
         for (std::size_t l = 0; l + 1 < grid.numLevels(); l++)
             if (!grid.levelAligned(l)) {
                 const auto& d = grid.getLevel(0).levelDim;

@@ -23,6 +23,7 @@
 #include "gpusolve_hip.h"
 #include "gpusolve_transfer.h"
 #include "gpusolve_line.h"
+#include "gpusolve_semi.h"
 #include "gs_comm.hpp"
 #include "gs_params.hpp"
 
@@ -110,6 +111,9 @@ public:
         std::array<std::size_t, 3> levelDim{}; // global interior extents
         double h = 0.0;
         gs_level geom{};     // kernel-side geometry of the stored array (slab or full level)
+        gs_stencil sten{};   // the level's stencil: the configuration's on every level of an XYZ hierarchy, the
+                             // re-discretised one (gs_semi_level_stencil) on level l of an XY hierarchy
+        bool line = false;   // the level smooths with z-line sweeps (setSmoother)
         bool distributed = false;
         bool fusedPairs = false; // smoothing runs as fused sweep pairs (gs_jacobi_sweep2)
         bool fusedTriples = false; // long LINEAR sweep sequences run as fused triples (gs_jacobi_sweep3)
@@ -129,8 +133,9 @@ public:
     // exchange, gather, norm reduction, swap and zeroing the solvers would issue is appended to *trace
     // as one "op key=value ..." line instead (gs_zslab_schedule; replayed by tests/test_zslab_cpu.py
     // with the oracle's arithmetic on gloo ranks).
+    // coarsen: GS_COARSEN_XYZ (0), GS_COARSEN_XY (1), or -1: what GS_COARSEN says (xyz without it).
     explicit HipGridData(const GridParams& grid, Comm* comm = nullptr, int64_t agglomeratePoints = -1,
-                         std::vector<std::string>* trace = nullptr);
+                         std::vector<std::string>* trace = nullptr, int coarsen = -1);
     ~HipGridData();
 
     LevelData& getLevel(std::size_t l) { return levels_[l]; }
@@ -203,7 +208,7 @@ public:
     // switched on. Throws, leaving the grid as it was.
     void setTransfer(int mode);
     bool levelAligned(std::size_t l) const; // the transition l -> l + 1 (l + 1 < numLevels())
-    bool pa(std::size_t l) const { return transferMode == 1 && !levelAligned(l); }
+    bool pa(std::size_t l) const { return !xy() && transferMode == 1 && !levelAligned(l); }
     const gs_transfer_tables* xfer(std::size_t l) const { return &xferT_[l]; }
     // The smoother (gs_grid_set_smoother, GS_SMOOTHER). 0, the default (JACOBI): damped point Jacobi,
     // every launch as before. 1 (ZLINE): HipSolver::jacobi runs one gs_zline_sweep (include/gpusolve_line.h) per sweep,
@@ -214,12 +219,29 @@ public:
     // What does not depend on the smoother stays: gs_residual_restrict, gs_prolong_add, the _pa launchers, the
     // zero-guess flag. LINEAR single-GPU grids whose stencil gs_zline_supported accepts; with GS_TRANSFER, GS_FMG and
     // GS_OMEGAS the switches that change the iterate.
+    // 2 (AUTO): level l runs z-line sweeps where the largest |z weight| of its stencil (LevelData::sten) is strictly
+    // greater than its largest |x / y weight|, the point path otherwise: all or nothing on an XYZ hierarchy, whose
+    // levels share one stencil; on an XY hierarchy typically the point kernels on the fine levels and lines below.
+    // A line level takes none of the steps that embed point Jacobi, a point level keeps its fused pairs and triples;
+    // the fused prolongation pair and the tiled steps are taken where the level they smooth is a point level (and the
+    // hierarchy is XYZ). One line level anywhere: no one-launch coarse cycle. The closing norm is speculated, and the
+    // norm wait overlapped, exactly when level 0 is a point level (the speculative step is a level-0 point sweep).
     int smootherMode = 0;
-    bool zline() const { return smootherMode == 1; }
-    // builds (gs_zline_factors) and uploads every level's factors the first time ZLINE is switched on; they are freed
-    // with the grid. Throws, leaving the grid as it was (zlineCheck: what a refusal says).
+    bool anyLine = false; // some level is a line level
+    bool lineAt(std::size_t l) const { return levels_[l].line; }
+    // builds (gs_zline_factors, from the level's own stencil) and uploads the factors of every line level that has
+    // none yet; they are freed with the grid. Throws, leaving the grid as it was (zlineCheck: what a refusal says).
     void setSmoother(int mode);
-    void zlineCheck() const;
+    void zlineCheck(const char* name = "ZLINE") const; // LINEAR, single GPU, level 0's stencil supported (ZLINE)
+    // The coarsening (gs_grid_create_coarsen, GS_COARSEN), fixed at creation. 0 (XYZ), the default:
+    // every axis halves per level. 1 (XY): x and y halve, nz stays; nlev = floor(log2(min(nx, ny))) + 1; level l has
+    // the stencil gs_semi_level_stencil gives for its h; every transition takes the general path with the _xy
+    // launchers of include/gpusolve_semi.h (tables of axes 0 and 1 built and uploaded at creation), whatever
+    // transferMode says — the fused prolongation pair, the tiled steps and the one-launch coarse cycle embed 3-D
+    // transfers and one stencil for several levels and are not taken; FMG is refused. LINEAR single-GPU grids whose
+    // stencil is the seven axis offsets, min(nx, ny) >= 2.
+    int coarsen = 0;
+    bool xy() const { return coarsen == 1; }
     const gs_zline_tables* zlineTables(std::size_t l) const { return &zlineT_[l]; }
     // Full multigrid's prolongation (gs_grid_set_fmg_prolong, GS_FMG_PROLONG). 0, the default (ALIGNED): gs_fmg_prolong
     // on aligned transitions only, so FMG starts at the deepest level above which every transition is aligned and is
@@ -330,6 +352,8 @@ private:
     std::vector<gs_fmg_tables> fmgT_;        // the same for gs_fmg_prolong_pa
     std::vector<gs_zline_tables> zlineT_;    // per level: the z-line factors (null pointers until ZLINE is first set)
     std::vector<void*> xferMem_;             // the device allocations behind all three
+    gs_transfer_tables uploadTransferTables(std::size_t l, int axes); // transition l -> l + 1 (3 axes, or x / y)
+    void buildXyTables();                    // the x / y tables of every transition of an XY hierarchy (creation)
     void updateCoarseFrom();                 // coarseFrom from coarseFromRef_, the transfers and the smoother
     bool haloPending_ = false; // an exchange issued by haloIssue, not settled
     friend class NewtonSolver;

@@ -25,6 +25,7 @@ from ._abi import GS_TRANSFER_POSITION, GS_TRANSFER_REFERENCE, gs_transfer_table
 from ._abi import GS_FMG_PROLONG_ALIGNED, GS_FMG_PROLONG_POSITION, gs_fmg_tables  # noqa: F401
 from ._abi import GS_PCG_BREAKDOWN, krylov  # noqa: F401
 from ._abi import GS_SMOOTHER_JACOBI, GS_SMOOTHER_ZLINE, gs_zline_tables, line  # noqa: F401
+from ._abi import GS_COARSEN_XY, GS_COARSEN_XYZ, GS_SMOOTHER_AUTO, semi  # noqa: F401
 
 CANONICAL_OFFSETS = [(0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)]
 
@@ -111,7 +112,8 @@ def _check(rc: int):
 
 _TRANSFERS = {"reference": GS_TRANSFER_REFERENCE, "position": GS_TRANSFER_POSITION}
 _FMG_PROLONGS = {"aligned": GS_FMG_PROLONG_ALIGNED, "position": GS_FMG_PROLONG_POSITION}
-_SMOOTHERS = {"jacobi": GS_SMOOTHER_JACOBI, "zline": GS_SMOOTHER_ZLINE}
+_SMOOTHERS = {"jacobi": GS_SMOOTHER_JACOBI, "zline": GS_SMOOTHER_ZLINE, "auto": GS_SMOOTHER_AUTO}
+_COARSENINGS = {"xyz": GS_COARSEN_XYZ, "xy": GS_COARSEN_XY}
 FIELDS = {"v": 0, "restV": 1, "newtonV": 2, "f": 3, "r": 4, "newtonF": 5}
 
 
@@ -125,10 +127,19 @@ class LevelInfo:
 class HipGridData:
     """Device-resident level hierarchy (fields in HBM for the object's lifetime)."""
 
-    def __init__(self, params: GridParams):
+    def __init__(self, params: GridParams, coarsen: str = None):
+        """coarsen: None (gs_grid_create: GS_COARSEN decides, xyz without it), "xyz", or "xy" — semi-coarsening for a
+        weak z coupling: x and y halve per level, nz stays, every level has its own stencil (level_stencil) and the
+        transfers do not touch z (include/gpusolve_semi.h). LINEAR single-GPU grids; GpuSolveError with the reason
+        otherwise."""
         self.params = params
         self._abi_params = params.to_abi()
-        self.handle = driver().gs_grid_create(C.byref(self._abi_params))
+        if coarsen is None:
+            self.handle = driver().gs_grid_create(C.byref(self._abi_params))
+        else:
+            if coarsen not in _COARSENINGS:
+                raise ValueError(f"coarsen must be one of {sorted(_COARSENINGS)}")
+            self.handle = driver().gs_grid_create_coarsen(C.byref(self._abi_params), _COARSENINGS[coarsen])
         if not self.handle:
             raise GpuSolveError(driver().gs_last_error().decode())
 
@@ -209,16 +220,40 @@ class HipGridData:
         z-column's tridiagonal system exactly and stays Jacobi across columns: include/gpusolve_line.h) — for stencils
         whose z weights dominate, where point Jacobi V-cycles stall; no gain on an isotropic stencil or a weak z axis.
         solve, vcycle, vcycle_from, jacobi, fmg and pcg follow it. GpuSolveError, with nothing changed, on a grid that
-        is not LINEAR, on a Z-slab grid, and for a stencil gs_zline_supported refuses."""
+        is not LINEAR, on a Z-slab grid, and for a stencil gs_zline_supported refuses. "auto" chooses per level: z-line
+        sweeps where the level stencil's largest |z weight| exceeds its largest |x / y weight|, the point path
+        otherwise (level_smoother) — all or nothing on an "xyz" grid, the point kernels on the fine levels and lines
+        below on an "xy" grid."""
         if mode not in _SMOOTHERS:
             raise ValueError(f"smoother must be one of {sorted(_SMOOTHERS)}")
         _check(driver().gs_grid_set_smoother(self.handle, _SMOOTHERS[mode]))
 
     @property
     def smoother(self) -> str:
-        """The smoother in force (set_smoother or GS_SMOOTHER): "jacobi" or "zline"."""
+        """The smoother in force (set_smoother or GS_SMOOTHER): "jacobi", "zline" or "auto"."""
         m = driver().gs_grid_get_smoother(self.handle)
         return next(k for k, v in _SMOOTHERS.items() if v == m)
+
+    @property
+    def coarsen(self) -> str:
+        """The coarsening the grid was created with: "xyz" or "xy"."""
+        m = driver().gs_grid_get_coarsen(self.handle)
+        return next(k for k, v in _COARSENINGS.items() if v == m)
+
+    def level_stencil(self, level: int) -> Stencil:
+        """The stencil level `level` runs with: the configuration's on an "xyz" grid, the re-discretised one
+        (gs_semi_level_stencil) on an "xy" grid."""
+        s = gs_stencil()
+        if driver().gs_grid_level_stencil(self.handle, level, C.byref(s)) != 0:
+            raise IndexError(level)
+        return Stencil([float(x) for x in s.s], [(s.ox[i], s.oy[i], s.oz[i]) for i in range(7)])
+
+    def level_smoother(self, level: int) -> str:
+        """"zline" where level `level` runs z-line sweeps, "jacobi" where it runs the point path."""
+        r = driver().gs_grid_level_smoother(self.handle, level)
+        if r < 0:
+            raise IndexError(level)
+        return "zline" if r else "jacobi"
 
     def set_fmg_prolong(self, mode: str):
         """Full multigrid's prolongation: "aligned" (the default: HipSolver.fmg needs sizes 2^k - 1) or "position"

@@ -14,6 +14,7 @@ KERNEL_LIB = os.path.join(LIB_DIR, "libgpusolve_hip.so")
 TRANSFER_LIB = os.path.join(LIB_DIR, "libgpusolve_transfer.so")  # position-aware transfers (include/gpusolve_transfer.h)
 KRYLOV_LIB = os.path.join(LIB_DIR, "libgpusolve_krylov.so")  # the PCG passes (include/gpusolve_krylov.h)
 LINE_LIB = os.path.join(LIB_DIR, "libgpusolve_line.so")  # the z-line smoother (include/gpusolve_line.h)
+SEMI_LIB = os.path.join(LIB_DIR, "libgpusolve_semi.so")  # XY semi-coarsening (include/gpusolve_semi.h)
 DIAG_LIB = os.path.join(LIB_DIR, "libgpusolve_diag.so")  # tools/ and tests/ only (include/gpusolve_diag.h)
 DRIVER_LIB = os.path.join(LIB_DIR, "libgpusolve_driver.so")
 EXECUTABLE = os.path.join(BIN_DIR, "GpuSolve-hip")
@@ -25,6 +26,9 @@ GS_EINVAL = 100001
 GS_TRANSFER_REFERENCE, GS_TRANSFER_POSITION = 0, 1  # gs_grid_set_transfer (include/gpusolve_driver.h)
 GS_FMG_PROLONG_ALIGNED, GS_FMG_PROLONG_POSITION = 0, 1  # gs_grid_set_fmg_prolong (include/gpusolve_driver.h)
 GS_SMOOTHER_JACOBI, GS_SMOOTHER_ZLINE = 0, 1  # gs_grid_set_smoother (include/gpusolve_driver.h)
+GS_SMOOTHER_AUTO = 2  # ... per level, by the level stencil's z weights against its x / y weights
+GS_COARSEN_XYZ, GS_COARSEN_XY = 0, 1  # gs_grid_create_coarsen (include/gpusolve_driver.h)
+GS_SEMI_RESIDUAL_RESTRICT, GS_SEMI_RESTRICT, GS_SEMI_PROLONG_ADD = 0, 1, 2  # gs_semi_kernel (include/gpusolve_semi.h)
 # include/gpusolve_krylov.h: the record's layout, its flag bits, and what gs_pcg_scalars does
 GS_PCG_RZ_I, GS_PCG_PQ_I, GS_PCG_ALPHA_I, GS_PCG_BETA_I, GS_PCG_RR_I, GS_PCG_FLAG_I, GS_PCG_REC = 0, 1, 2, 3, 4, 5, 8
 GS_PCG_BAD_PQ, GS_PCG_BAD_RZ, GS_PCG_BAD_RR = 1, 2, 4
@@ -220,9 +224,27 @@ LINE_API = {
     "gs_zline_kernel": (C.c_char_p, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int]),
 }
 
+# libgpusolve_semi.so (include/gpusolve_semi.h): XY semi-coarsening — level stencils and the transfers without z
+SEMI_API = {
+    "gs_semi_level_stencil": (C.c_int, [C.POINTER(gs_stencil), C.c_double, C.c_double, C.POINTER(gs_stencil)]),
+    "gs_restrict_xy": (C.c_int, [C.c_void_p, C.POINTER(gs_level), C.c_void_p, C.POINTER(gs_level),
+                                 C.POINTER(gs_transfer_tables), C.c_void_p]),
+    "gs_prolong_add_xy": (C.c_int, [C.c_void_p, C.POINTER(gs_level), C.c_void_p, C.POINTER(gs_level),
+                                    C.POINTER(gs_transfer_tables), C.c_void_p]),
+    "gs_residual_restrict_xy": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.POINTER(gs_level), C.POINTER(gs_transfer_tables), C.c_void_p]),
+    "gs_semi_kernel": (C.c_char_p, [C.c_int, C.POINTER(gs_level), C.POINTER(gs_level)]),
+    "gs_semi_launch_dry_run": (C.c_int, [C.c_int]),
+    "gs_semi_launch_record": (i64, [C.c_char_p, i64]),
+}
+
 DRIVER_API = {
     "gs_parse_config": (C.c_int, [C.c_char_p, C.POINTER(gs_params)]),
     "gs_grid_create": (C.c_void_p, [C.POINTER(gs_params)]),
+    "gs_grid_create_coarsen": (C.c_void_p, [C.POINTER(gs_params), C.c_int]),
+    "gs_grid_get_coarsen": (C.c_int, [C.c_void_p]),
+    "gs_grid_level_stencil": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(gs_stencil)]),
+    "gs_grid_level_smoother": (C.c_int, [C.c_void_p, C.c_int]),
     "gs_grid_destroy": (None, [C.c_void_p]),
     "gs_grid_solve": (C.c_int, [C.c_void_p, C.c_int, dptr, C.c_int, C.POINTER(C.c_int)]),
     "gs_grid_vcycle": (C.c_int, [C.c_void_p, dptr]),
@@ -356,6 +378,12 @@ def line():
     return _load(LINE_LIB, LINE_API)
 
 
+def semi():
+    """The XY semi-coarsening library (libgpusolve_semi.so)."""
+    kernels()
+    return _load(SEMI_LIB, SEMI_API)
+
+
 def diag():
     """The diagnostics library (libgpusolve_diag.so): measurement and tuning code, never the product path."""
     kernels()
@@ -367,4 +395,5 @@ def driver():
     transfer()
     krylov()
     line()
+    semi()
     return _load(DRIVER_LIB, DRIVER_API)

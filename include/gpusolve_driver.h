@@ -40,6 +40,26 @@ typedef struct {
 int gs_parse_config(const char* text, gs_params* out);
 
 void* gs_grid_create(const gs_params* p); /* device-resident hierarchy on the current HIP device */
+/* The coarsening, a creation-time choice (added). GS_COARSEN_XYZ: gs_grid_create, launch for launch.
+ * GS_COARSEN_XY: semi-coarsening for a stencil whose z coupling is weak — level l has (nx_{l-1} / 2, ny_{l-1} / 2, nz)
+ * points, nlev = floor(log2(min(nx, ny))) + 1, and its own stencil, re-discretised by gs_semi_level_stencil of
+ * gpusolve_semi.h (gs_grid_level_stencil reads it; on an XYZ grid every level reports the configuration's). Every
+ * transition takes the general path with that header's _xy launchers (by-position tables in x and y, built and
+ * uploaded once, at creation; every size works) between the level's ordinary sweeps: point levels keep their fused
+ * pairs and triples, line levels their z-line sweeps (gs_grid_set_smoother; GS_SMOOTHER_AUTO picks per level). The
+ * fused prolongation pair, the tiled steps and the one-launch coarse cycle are not taken, gs_grid_set_transfer changes
+ * nothing and gs_grid_fmg is refused with a reason. gs_grid_solve, gs_grid_vcycle, gs_grid_vcycle_level,
+ * gs_grid_pcg (R_xy is the scaled transpose of P_xy: its conditions on the transfers hold on every size), per-sweep
+ * weights, gs_grid_jacobi and gs_grid_residual_norm work as on any grid. NULL, with the reason in gs_last_error() and
+ * nothing allocated: any other `coarsen`; XY with a mode other than LINEAR, a stencil that is not the seven axis
+ * offsets once each, or min(nx, ny) < 2 (XY on a Z-slab / RCCL or schedule-trace grid is refused the same way where
+ * GS_COARSEN asks for it). GS_COARSEN=xy|xyz in the environment when a grid is created chooses for gs_grid_create and
+ * GpuSolve-hip; any other value fails the creation. gs_grid_create_coarsen does not read the variable. */
+enum { GS_COARSEN_XYZ = 0, GS_COARSEN_XY = 1 };
+void* gs_grid_create_coarsen(const gs_params* p, int coarsen);
+int gs_grid_get_coarsen(void* grid);
+/* The stencil level `level` runs with. 1 for a bad level or a NULL `out`. */
+int gs_grid_level_stencil(void* grid, int level, gs_stencil* out);
 void gs_grid_destroy(void* grid);
 
 /* Runs the solve selected by the mode. print: 0 silent, 1 reference stdout lines.
@@ -162,10 +182,23 @@ int gs_grid_get_transfer(void* grid);
  * ZLINE is first switched on and freed with the grid. Fails (return 1, gs_last_error(), nothing changed) for any
  * other mode value and for ZLINE on a grid that is not LINEAR, on a Z-slab / RCCL or schedule-trace grid (the lines
  * cross the slabs) and for a stencil gs_zline_supported refuses. GS_SMOOTHER=zline|jacobi in the environment when the
- * grid is created sets the mode; any other value, and zline on such a grid, fails the creation. */
-enum { GS_SMOOTHER_JACOBI = 0, GS_SMOOTHER_ZLINE = 1 };
+ * grid is created sets the mode; any other value, and zline on such a grid, fails the creation.
+ * GS_SMOOTHER_AUTO (added; "auto" in GS_SMOOTHER) chooses per level: level l runs z-line sweeps where
+ * the largest |z weight| of its stencil (gs_grid_level_stencil) is strictly greater than its largest |x / y weight|,
+ * and the point path otherwise (gs_grid_level_smoother reports the choice). On an XYZ grid all levels share one
+ * stencil, so AUTO is all or nothing; on an XY grid every coarsening multiplies the z weights by four against the
+ * others, so the fine levels stay on the fused point kernels and the levels below run lines. JACOBI and ZLINE still
+ * mean every level; on an XY grid ZLINE builds each level's factors from that level's stencil. A point level keeps
+ * its fused pairs and triples, a line level takes nothing that embeds point Jacobi; one line level anywhere rules out
+ * the one-launch coarse cycle. The closing norm: speculation, and with it the overlap of the norm wait, is off
+ * whenever level 0 is a line level (the norm comes from a residual pass) and unchanged otherwise. AUTO needs a LINEAR
+ * single-GPU grid, as ZLINE does, and is refused, with nothing changed, when a level that would run line sweeps has a
+ * stencil gs_zline_supported refuses. */
+enum { GS_SMOOTHER_JACOBI = 0, GS_SMOOTHER_ZLINE = 1, GS_SMOOTHER_AUTO = 2 };
 int gs_grid_set_smoother(void* grid, int mode);
 int gs_grid_get_smoother(void* grid);
+/* 1 if level `level` runs z-line sweeps, 0 if it runs the point path, -1 for a bad level. */
+int gs_grid_level_smoother(void* grid, int level);
 /* Full multigrid's prolongation (added; DESIGN.md §4.7 "FMG on every size"). GS_FMG_PROLONG_ALIGNED, the default:
  * gs_grid_fmg as described above, unchanged launch for launch. GS_FMG_PROLONG_POSITION: gs_grid_fmg_start_level is the
  * coarsest level on every LINEAR / NONLINEAR single-GPU grid (NEWTON, Z-slab and trace grids: still 0, still refused);
@@ -179,8 +212,8 @@ int gs_grid_get_smoother(void* grid);
 enum { GS_FMG_PROLONG_ALIGNED = 0, GS_FMG_PROLONG_POSITION = 1 };
 int gs_grid_set_fmg_prolong(void* grid, int mode);
 int gs_grid_get_fmg_prolong(void* grid);
-/* 1 if the transition from `level` to `level + 1` is aligned (fine n = 2 coarse n + 1 on all three axes), 0 if not,
- * -1 if there is no such transition. */
+/* 1 if the transition from `level` to `level + 1` is aligned (fine n = 2 coarse n + 1 on all three axes; on an XY
+ * grid: on x and y), 0 if not, -1 if there is no such transition. */
 int gs_grid_level_aligned(void* grid, int level);
 int gs_grid_jacobi(void* grid, int level, int sweeps);
 int gs_grid_residual_norm(void* grid, int level, double* norm);
