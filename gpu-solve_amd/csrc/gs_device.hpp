@@ -609,6 +609,18 @@ __device__ __forceinline__ void sa_st2nt(uint64_t base, unsigned off, double a, 
 }
 __device__ __forceinline__ void sa_st1(uint64_t base, unsigned off, double a) { *reinterpret_cast<sa_d*>(base + off) = a; }
 
+// A copy the register coalescer cannot fold (k_tb3y's staggered instance): the value moves into registers of its own (the
+// early-clobber output), so the source's registers stay the source's. Where a load slot's rows are handed over to the
+// plane state with plain assignments, the state takes over the slot's registers, the refill lands in others, and the
+// loop-carried slot is put back under its header name by copies on the back-edge that wait for the refill.
+__device__ __forceinline__ double2 mov_fresh(const double2 a)
+{
+    double2 r;
+    asm("v_mov_b64 %0, %1" : "=&v"(r.x) : "v"(a.x));
+    asm("v_mov_b64 %0, %1" : "=&v"(r.y) : "v"(a.y));
+    return r;
+}
+
 // Loads of the iterate; ZV: the iterate is identically zero (a coarse level's first sweep after
 // the reference's v = 0) and is not read at all. Multiplying the literal zeros keeps the arithmetic,
 // and so every bit of the result, that of loaded zeros (no fast-math folding).
@@ -3031,6 +3043,12 @@ constexpr int tby_pfd(int mode) { return mode == GS_LINEAR ? 2 : 1; }
 // consumed yet. The lagging half runs its own copy of the whole z loop (`half` below): in one loop with a branch per
 // step each half carries the other's state through its steps as live values, the two do not fit 256 VGPRs together,
 // and loads issued on one path only turn the compiler's counted vmcnt waits into vmcnt(0) where the paths join.
+// ST also hands a load slot's v rows over to the plane state with a real move (mov_fresh) and keeps f's two parity slots
+// in registers (FR: 24 VGPRs, moved out of the load slot the same way; no f1_l, 49,152 B of LDS and 3 of a lane's 6
+// ds_write_b128 / ds_read_b128 per step less). With plain assignments the plane state takes over the slot's registers,
+// the refill lands in others, and the copies that put the loop-carried slot back on the back-edge waited for loads
+// half a step old (vmcnt(4) in the lagging loop). Now every vmcnt wait of both z loops leaves the newest slot's nine
+// loads in flight and the back-edge blocks hold none (tools/waits_table.py prints them; 230 VGPRs, 52,608 B LDS).
 // GS_EXP_T3_FLIGHT / GS_EXP_T3_CHAIN: the two timing-only probes of the step's shape (top of this file).
 #ifdef GS_EXP_T3_CHAIN
 #define GS_T3_ZP(n, c) c
@@ -3054,13 +3072,15 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
 #else
     constexpr bool ST = SA && FX; // the staggered step: the mirrored y-waves (wy = 1) run half a step behind (above)
 #endif
+    constexpr bool FR = ST; // f's two parity slots (f1_l below) in registers, not in LDS: this instance has the room
     // x-edges: [parity][y-wave][1 + x-wave][side][value]; x-wave slots 0 and WX+1 are the zero x-boundary columns
     __shared__ double edge[2][2][WXMAX + 2][2][NE];
     // y-edge rows: [parity][y-wave][x-wave][v | sweep-1 | sweep-2][lane]
     __shared__ double2 yrow[2][2][WXMAX][3][WAVE];
     // per-lane state, [row][wave][lane]: f at planes z-1 / z (rows 0..RY) and z-2 (rows 1..RY), sweep 1 at plane z-2
     // (rows 0..RY), sweep 2 at plane z-3 (rows 1..RY)
-    // (f1_l: two slots by step parity; sweep 1 writes f(z+1) into the slot sweep 2 reads two steps later)
+    // (f1_l: two slots by step parity; sweep 1 writes f(z+1) into the slot sweep 2 reads two steps later. FR: in
+    // registers, F1s below; the array is not referenced then and takes no LDS)
     __shared__ double2 f1_l[2][N1][2 * WXMAX][WAVE];
     __shared__ double2 f2_l[RY][2 * WXMAX][WAVE];
     __shared__ double2 s1p_l[N1][2 * WXMAX][WAVE];
@@ -3113,12 +3133,14 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
         double2 Vp[N0], Vc[N0], VL[2][N0], FL[2][N0], HL[2]; // v(z), v(z+1); per slot: v(z+2), f(z+1), v(z+1) at row -2
         double2 S1a[N0], S1c[N0], S2c[N1];                   // sweep 1 at planes z and z-1, sweep 2 at plane z-2
         double2 S1p[N1], S2p[RY], F2[RY];                    // RS: sweep 1 at plane z-2, sweep 2 at plane z-3, f at plane z-2
+        double2 F1s[2][N1];                                  // FR: f1_l's two slots
 #pragma unroll
         for (int i = 0; i < N0; i++) S1a[i] = S1c[i] = make_double2(0.0, 0.0);
 #pragma unroll
         for (int i = 0; i < N1; i++) {
             S2c[i] = make_double2(0.0, 0.0);
-            f1_l[0][i][wid][lane] = f1_l[1][i][wid][lane] = make_double2(0.0, 0.0);
+            if constexpr (FR) F1s[0][i] = F1s[1][i] = make_double2(0.0, 0.0);
+            else f1_l[0][i][wid][lane] = f1_l[1][i][wid][lane] = make_double2(0.0, 0.0);
             if constexpr (RS) S1p[i] = make_double2(0.0, 0.0);
             else s1p_l[i][wid][lane] = make_double2(0.0, 0.0);
         }
@@ -3275,7 +3297,8 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
                         double q[2 * B2];
 #pragma unroll
                         for (int i = b; i < b + B2; i++) {
-                            F1[i] = f1_l[LAG ? cs : ph][i][wid][lane];
+                            if constexpr (FR) F1[i] = F1s[LAG ? cs : ph][i];
+                            else F1[i] = f1_l[LAG ? cs : ph][i][wid][lane];
                             row_sums(mirc, S1c[i + 1], S1c[i], i == N1 - 1 ? s1Y : S1c[i + 2],
                                      RS ? S1p[i] : s1p_l[i][wid][lane],
                                      GS_T3_ZP(S1a[i + 1], S1c[i + 1]),
@@ -3352,11 +3375,19 @@ __global__ __launch_bounds__(WAVE* TBY_WX * 2) void k_tb3y(Coef k, const double*
                 // ---- ... and of sweep 1: f into the slot sweep 2 reads, v one plane on
                 auto rotate1 = [&] {
 #pragma unroll
-                    for (int i = 0; i < N1; i++) f1_l[ph][i][wid][lane] = FL[cs][i + 1];
+                    for (int i = 0; i < N1; i++) {
+                        if constexpr (FR) F1s[ph][i] = mov_fresh(FL[cs][i + 1]); // (a real move, as v's below)
+                        else f1_l[ph][i][wid][lane] = FL[cs][i + 1];
+                    }
 #pragma unroll
                     for (int i = 0; i < N0; i++) {
                         Vp[i] = Vc[i];
-                        Vc[i] = VL[cs][i];
+                        // (ST: a real move. The slot keeps its registers from one iteration to the next, its refill
+                        // writes them, and nothing reads them before the refill's first consumer, so no copy on the
+                        // back-edge waits for loads in flight. The other instances are at the register limit and keep
+                        // the assignment, `if constexpr` so that their code is the same to the instruction)
+                        if constexpr (ST) Vc[i] = mov_fresh(VL[cs][i]);
+                        else Vc[i] = VL[cs][i];
                     }
                 };
                 if constexpr (LAG) {

@@ -753,11 +753,11 @@ const char* gs_strerror(int code)
 
 const char* gs_build_info(void)
 {
-    return "gpusolve_hip v18: LINEAR triples k_tb3y(the pair's whole-row tile, three sweeps per pass, sweep 1 one plane "
+    return "gpusolve_hip v19: LINEAR triples k_tb3y(the pair's whole-row tile, three sweeps per pass, sweep 1 one plane "
            "ahead and last in the step, whole-wave rows: the mirrored y-waves half a step behind (sweep 1 first, own z "
-           "loop, s_setprio 1), two load slots, scalar row bases + 32-bit lane offsets, "
-           "previous-plane rows in registers, per-lane f in LDS, x-edge values read row by row from LDS into the DPP "
-           "shift), "
+           "loop, s_setprio 1), two load slots that keep their registers across the back-edge, scalar row bases + 32-bit "
+           "lane offsets, previous-plane rows in registers, per-lane f in LDS (whole-wave rows: in registers), x-edge "
+           "values read row by row from LDS into the DPP shift), "
            "pairs k_tb2y(4x2 waves, 2 rows/wave, one round of z-chunks on large levels, LINEAR 2-step prefetch; +prolong; "
            "512-point column blocks for longer rows in every mode; from 64^3 levels; zero-iterate chunks fitted to "
            "resident rounds; zero iterates q = +0; whole-wave rows without range selects (FX); LINEAR loads grouped by "
