@@ -57,15 +57,22 @@ bool overlap(const gs_level* L, const double* a, const double* b)
 // on. Its ring of loads in flight matters more than full waves on the coarse levels, which are load latency times
 // 2 nz steps: with the threshold at 128 * 128 the 127^3 and 63^3 levels made a 255^3 cycle 2.11 ms
 constexpr int64_t ZL_MARCH_COLUMNS = 32 * 32;
+// the LDS instance: below that column count, in any order, where the planes fit its static array (ZF_MAX_NZ) and are
+// enough to pay for its two barriers (ZF_MIN_NZ). Such a level is 2 nz dependent global loads in k_zline_col, a
+// fraction of one CU's lanes wide: five of them were 9.6 of a 15.4 ms XY cycle at 511^3
 struct ZlPlan {
-    bool march;
+    bool march, lds;
     dim3 grid;
     bool ok; // the grid is launchable
 };
 ZlPlan zl_plan(const gs_stencil* S, const gs_level* L)
 {
-    ZlPlan p{canonical_order(S) && L->nx * L->ny >= ZL_MARCH_COLUMNS, dim3(1), true};
-    if (p.march) {
+    const int64_t columns = L->nx * L->ny;
+    ZlPlan p{canonical_order(S) && columns >= ZL_MARCH_COLUMNS, false, dim3(1), true};
+    p.lds = columns < ZL_MARCH_COLUMNS && L->nz >= ZF_MIN_NZ && L->nz <= ZF_MAX_NZ;
+    if (p.lds) {
+        p.grid = dim3((unsigned)((columns + ZF_CB - 1) / ZF_CB)); // at most 128 blocks
+    } else if (p.march) {
         const int64_t nb = ((L->nx + 2 * WAVE - 1) / (2 * WAVE)) * ((L->ny + ZL_W - 1) / ZL_W);
         p.ok = nb <= INT32_MAX;
         p.grid = dim3((unsigned)nb);
@@ -110,6 +117,7 @@ const char* gs_zline_kernel(const gs_stencil* S, const gs_level* L, int zero)
     if (!zl_supported(S, &z) || bad_line_level(L) || empty_level(L)) return "";
     const ZlPlan p = zl_plan(S, L);
     if (!p.ok) return "";
+    if (p.lds) return zero ? "k_zline_lds<true>" : "k_zline_lds<false>";
     if (p.march) return zero ? "k_zline_march<true>" : "k_zline_march<false>";
     return zero ? "k_zline_col<true>" : "k_zline_col<false>";
 }
@@ -134,7 +142,10 @@ int gs_zline_sweep(const gs_stencil* S, const gs_level* L, double omega, const d
     k.omega = omega;
     const int nx = (int)L->nx, ny = (int)L->ny, nz = (int)L->nz;
     with_bools([&](auto ZV) {
-        if (p.march)
+        if (p.lds)
+            launch((k_zline_lds<ZV>), p.grid, dim3(ZF_T), st, k, v_in, f, v_out, T->cp, T->den, nx, ny, nz, L->ldy,
+                   L->ldz);
+        else if (p.march)
             launch((k_zline_march<ZV>), p.grid, dim3(WAVE, ZL_W), st, k, v_in, f, v_out, T->cp, T->den, nx, ny, nz,
                    L->ldy, L->ldz);
         else

@@ -195,4 +195,119 @@ __global__ __launch_bounds__(256) void k_zline_col(ZlCoef k, const double* __res
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Few, long columns (fewer than 32 * 32 of them, ZF_MIN_NZ .. ZF_MAX_NZ planes; any stencil order): k_zline_col's
+// 2 nz dependent steps each wait for a global load there, on levels that fill a fraction of one CU. Here a block of
+// four waves owns ZF_CB columns (consecutive in the flattened index x - 1 + nx * (y - 1), so the tiles are full
+// whatever nx is) and keeps their state in LDS, [plane][column]:
+//   A  all threads, one (plane, column) each per pass of ZF_T / ZF_CB planes: b_k into LDS, k_zline_col's expression
+//      with the neighbours at the entries' linear offsets; den[1 .. nz] and cp[1 .. nz] into LDS beside it
+//   B  lanes 0 .. ZF_CB - 1 of wave 0, a column each: d over b, k ascending, then u over d, k descending. As in
+//      k_zline_march the operands of the next planes wait in a register ring (a slot is consumed, then refilled from
+//      LDS with the plane one ring length ahead; the loops are unrolled by the ring length), so that no step waits
+//      for memory: the step is the chain itself (multiply, subtract, IEEE divide; multiply, subtract)
+//   C  all threads: the relaxed iterate from u (LDS) and v (global) to the interior of v_out
+// d never leaves LDS and v_out is never read: 24 B per point (16 on the zero iterate) where k_zline_col moves 48.
+// The steps of B past the level's end are computed and discarded, as in k_zline_march: their operands are read at
+// the plane clamped into 1 .. nz, and their results land in spare rows below plane 1 and above plane nz.
+// Every thread reaches both barriers: a thread without a column, or a wave without a chain, only skips its work.
+constexpr int ZF_T = 256;     // threads per block
+constexpr int ZF_CB = 8;      // columns per block
+// Ring lengths. Forward: a step is a dozen dependent fp64 instructions, three steps cover an LDS read many times
+// over, and the 3 * (2 reads + 1 write) behind a slot's read stay under lgkmcnt's 15: its waits are exact. Backward: a
+// step is two operations, so the ring is longer.
+constexpr int ZF_UF = 4, ZF_UB = 8;
+constexpr int ZF_MIN_NZ = 64; // below: a launch is mostly phases A and C, and k_zline_col's is as short
+constexpr int ZF_MAX_NZ = 1536;
+constexpr int ZF_ROWS = ZF_MAX_NZ + ZF_UB + ZF_UF - 2;    // planes 2 - ZF_UB .. ZF_MAX_NZ + ZF_UF - 1
+constexpr int ZF_WORDS = ZF_ROWS * ZF_CB + 2 * ZF_MAX_NZ; // state, den[1 ..], cp[1 ..]: 123,520 B
+static_assert(ZF_WORDS * sizeof(double) <= 160 * 1024, "k_zline_lds: static LDS beyond a CU's 160 KiB");
+
+template <bool ZV>
+__global__ __launch_bounds__(ZF_T) void k_zline_lds(ZlCoef k, const double* __restrict__ v, const double* __restrict__ f,
+                                                    double* __restrict__ out, const double* __restrict__ cp,
+                                                    const double* __restrict__ den, int nx, int ny, int nz, int64_t ldy,
+                                                    int64_t ldz)
+{
+    __shared__ double lds[ZF_WORDS]; // one array: state rows, then the two tables
+    double* const S = lds + (ZF_UB - 2) * ZF_CB; // S[kz * ZF_CB + c]: plane kz (2 - ZF_UB .. nz + ZF_UF - 1), column c
+    double* const DEN = lds + ZF_ROWS * ZF_CB - 1; // DEN[kz], CP[kz]: kz = 1 .. nz
+    double* const CP = DEN + ZF_MAX_NZ;
+    const int t = threadIdx.x;
+    const int c = t % ZF_CB, pz = t / ZF_CB;
+    const int col = blockIdx.x * ZF_CB + c;
+    const bool has = col < nx * ny;
+    const int64_t base = (1 + col % nx) + (int64_t)(1 + col / nx) * ldy;
+
+    // ---- A ----
+    if (has) {
+#pragma unroll 4
+        for (int kz = 1 + pz; kz <= nz; kz += ZF_T / ZF_CB) {
+            const int64_t p = base + (int64_t)kz * ldz;
+            double b = k.hh * f[p];
+            if (!ZV) b = b - zl_g(k, v[p + k.off[0]], v[p + k.off[1]], v[p + k.off[2]], v[p + k.off[3]]);
+            S[kz * ZF_CB + c] = b;
+        }
+    }
+    for (int kz = 1 + t; kz <= nz; kz += ZF_T) {
+        DEN[kz] = den[kz];
+        CP[kz] = cp[kz];
+    }
+    __syncthreads();
+
+    // ---- B ----
+    if (t < ZF_CB && has) {
+        {
+            double X[ZF_UF], W[ZF_UF]; // the ring: b_k and den[k] of the next ZF_UF planes
+#pragma unroll
+            for (int s = 0; s < ZF_UF; s++) {
+                const int q = min(1 + s, nz);
+                X[s] = S[q * ZF_CB + c];
+                W[s] = DEN[q];
+            }
+            double d = 0.0;
+            for (int k0 = 1; k0 <= nz; k0 += ZF_UF) {
+#pragma unroll
+                for (int s = 0; s < ZF_UF; s++) {
+                    const int kz = k0 + s, q = min(kz + ZF_UF, nz);
+                    d = zl_fwd(k, X[s], d, W[s], kz == 1);
+                    X[s] = S[q * ZF_CB + c];
+                    W[s] = DEN[q];
+                    S[kz * ZF_CB + c] = d;
+                }
+            }
+        }
+        {
+            double X[ZF_UB], W[ZF_UB]; // d_k and cp[k]
+#pragma unroll
+            for (int s = 0; s < ZF_UB; s++) {
+                const int q = max(nz - s, 1);
+                X[s] = S[q * ZF_CB + c];
+                W[s] = CP[q];
+            }
+            double u = 0.0;
+            for (int k0 = nz; k0 >= 1; k0 -= ZF_UB) {
+#pragma unroll
+                for (int s = 0; s < ZF_UB; s++) {
+                    const int kz = k0 - s, q = max(kz - ZF_UB, 1);
+                    u = zl_bwd(X[s], u, W[s], kz == nz);
+                    X[s] = S[q * ZF_CB + c];
+                    W[s] = CP[q];
+                    S[kz * ZF_CB + c] = u;
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- C ----
+    if (has) {
+#pragma unroll 4
+        for (int kz = 1 + pz; kz <= nz; kz += ZF_T / ZF_CB) {
+            const int64_t p = base + (int64_t)kz * ldz;
+            out[p] = zl_relax<ZV>(k, ZV ? 0.0 : v[p], S[kz * ZF_CB + c]);
+        }
+    }
+}
+
 } // namespace

@@ -24,7 +24,8 @@
  *
  * d lives in v_out between the two passes: each element is written in the forward pass and read back, then
  * overwritten with the result, by the lane that wrote it. One launch per sweep; no field beyond v_in's ping-pong
- * partner is needed.
+ * partner is needed. The instance for few, long columns (k_zline_lds, below) keeps d in LDS instead: it never reads
+ * v_out and writes each interior element once, with the result.
  *
  * Conventions of gpusolve_hip.h: asynchronous on `stream`, no allocation, no copy, no synchronisation, no environment
  * variable; 0, GS_EINVAL or a hipError_t. Layout contract: any legal pitch and any 8-byte-aligned field pointer;
@@ -69,8 +70,10 @@ int gs_zline_sweep(const gs_stencil* S, const gs_level* L, double omega, const d
 
 /* The kernel instance gs_zline_sweep launches for (S, L, v_in == NULL ? zero : !zero): "k_zline_march<zero>" — a lane
  * owns a pair of columns and marches up, then down, with a register ring of planes in flight; canonical stencil
- * order and at least 32 * 32 columns — or "k_zline_col<zero>" (a thread owns one column: every other
- * order, and the small levels); "" for arguments the sweep refuses and for a level with an empty axis. */
+ * order and at least 32 * 32 columns — "k_zline_lds<zero>" — a block owns eight columns, keeps their state in LDS
+ * and runs the two recurrences out of it; fewer than 32 * 32 columns and 64 <= nz <= 1536, in any order — or
+ * "k_zline_col<zero>" (a thread owns one column: every other level); "" for arguments the sweep refuses and for a
+ * level with an empty axis. The three compute the same words. */
 const char* gs_zline_kernel(const gs_stencil* S, const gs_level* L, int zero);
 
 #ifdef __cplusplus
