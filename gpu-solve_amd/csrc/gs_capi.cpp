@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gpusolve_driver.h"
+#include "gpusolve_io.h"
 #include "gs_grid.hpp"
 
 namespace {
@@ -55,6 +56,13 @@ gs::GridParams toParams(const gs_params* p)
 struct Handle {
     std::unique_ptr<gs::Comm> comm;
     std::unique_ptr<gs::HipGridData> grid;
+    // gs_grid_import / gs_grid_export: [0] the user's stream -> the grid's, [1] back; created on first use
+    hipEvent_t ioEv[2] = {nullptr, nullptr};
+    ~Handle()
+    {
+        for (hipEvent_t e : ioEv)
+            if (e) (void)hipEventDestroy(e);
+    }
 };
 
 gs::HipGridData& G(void* h) { return *static_cast<Handle*>(h)->grid; }
@@ -404,6 +412,57 @@ int gs_grid_upload(void* grid, int level, int field, const double* host)
 {
     if (!host) return 1;
     return copy_field(grid, level, field, nullptr, host);
+}
+
+// gs_grid_import / gs_grid_export: everything is checked before the field's state is touched (field_ptr's writable
+// side effect included) and before anything is enqueued; no host synchronisation anywhere
+static int io_field(void* grid, int level, int field, void* dev, int dtype, const int64_t* stride, double scale,
+                    hipStream_t user, bool import)
+{
+    return guarded([&] {
+        const char* who = import ? "gs_grid_import" : "gs_grid_export";
+        auto* h = static_cast<Handle*>(grid);
+        auto& g = G(grid);
+        if (g.trace || g.nranks() > 1)
+            throw gs::Error(std::string(who) + " needs a single-GPU grid: a Z-slab rank holds a slab of the level, "
+                            "whose ghost planes would need an exchange");
+        if (level < 0 || level >= (int)g.numLevels()) throw gs::Error(std::string(who) + ": no such level");
+        if (!field_ptr(grid, level, field, false)) throw gs::Error("no such field on this level");
+        if (!dev || !stride) throw gs::Error(std::string(who) + ": null device pointer or strides");
+        const gs_level& L = g.getLevel(level).geom;
+        const int dir = import ? GS_IO_IMPORT : GS_IO_EXPORT;
+        if (!std::isfinite(scale) || !*gs_io_kernel(dir, dtype, &L, stride))
+            throw gs::Error(std::string(who) + ": invalid argument (include/gpusolve_io.h: dtype, strides " +
+                            (import ? ">= 0" : ">= 1 that do not alias") + ", a finite scale)");
+        const hipStream_t gst = g.stream();
+        const bool cross = user != gst;
+        if (cross) {
+            for (hipEvent_t& e : h->ioEv)
+                if (!e) gs::check((int)hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
+            gs::check((int)hipEventRecord(h->ioEv[0], user), "hipEventRecord");
+            gs::check((int)hipStreamWaitEvent(gst, h->ioEv[0], 0), "hipStreamWaitEvent");
+        }
+        double* d = field_ptr(grid, level, field, import);
+        gs::check(import ? gs_io_import(d, &L, dev, dtype, stride, scale, gst)
+                         : gs_io_export(d, &L, dev, dtype, stride, scale, gst),
+                  import ? "gs_io_import" : "gs_io_export");
+        if (cross) {
+            gs::check((int)hipEventRecord(h->ioEv[1], gst), "hipEventRecord");
+            gs::check((int)hipStreamWaitEvent(user, h->ioEv[1], 0), "hipStreamWaitEvent");
+        }
+    });
+}
+
+int gs_grid_import(void* grid, int level, int field, const void* dev, int dtype, const int64_t stride[3], double scale,
+                   hipStream_t user)
+{
+    return io_field(grid, level, field, const_cast<void*>(dev), dtype, stride, scale, user, true);
+}
+
+int gs_grid_export(void* grid, int level, int field, void* dev, int dtype, const int64_t stride[3], double scale,
+                   hipStream_t user)
+{
+    return io_field(grid, level, field, dev, dtype, stride, scale, user, false);
 }
 
 // Vector3::dump (src/cpu/Vector3.cpp:56-78): with a file, the header "Px Py Pz" then one line

@@ -26,6 +26,7 @@ from ._abi import GS_FMG_PROLONG_ALIGNED, GS_FMG_PROLONG_POSITION, gs_fmg_tables
 from ._abi import GS_PCG_BREAKDOWN, krylov  # noqa: F401
 from ._abi import GS_SMOOTHER_JACOBI, GS_SMOOTHER_ZLINE, gs_zline_tables, line  # noqa: F401
 from ._abi import GS_COARSEN_XY, GS_COARSEN_XYZ, GS_SMOOTHER_AUTO, semi  # noqa: F401
+from ._abi import GS_IO_EXPORT, GS_IO_F32, GS_IO_F64, GS_IO_IMPORT, io  # noqa: F401
 
 CANONICAL_OFFSETS = [(0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)]
 
@@ -142,6 +143,11 @@ class HipGridData:
             self.handle = driver().gs_grid_create_coarsen(C.byref(self._abi_params), _COARSENINGS[coarsen])
         if not self.handle:
             raise GpuSolveError(driver().gs_last_error().decode())
+        # the device the grid lives on (the current one at creation): load / store hold their tensors to it. The
+        # HIP runtime is among the driver library's dependencies, so its symbols resolve through the handle.
+        dev = C.c_int(-1)
+        driver().hipGetDevice(C.byref(dev))
+        self.device_index = dev.value
 
     def close(self):
         if getattr(self, "handle", None):
@@ -310,6 +316,65 @@ class HipGridData:
         host = np.ascontiguousarray(np.asarray(arr_xyz, dtype=np.float64).transpose(2, 1, 0))
         assert host.shape == (g.nz + 2, g.ny + 2, g.nx + 2)
         _check(driver().gs_grid_upload(self.handle, level, FIELDS[name], host.ctypes.data_as(_abi.dptr)))
+
+    def _io_call(self, name, t, level, scale, order):
+        """Checks a tensor against a field of `level` (ValueError before any driver call) and returns gs_grid_import's
+        / gs_grid_export's arguments after the grid handle: the tensor's own strides, by grid axis, through `order`."""
+        import torch
+
+        if name not in FIELDS:
+            raise ValueError(f"field must be one of {sorted(FIELDS)}")
+        if not isinstance(order, str) or sorted(order) != ["x", "y", "z"]:
+            raise ValueError('order must be a permutation of "xyz" naming the tensor\'s index order')
+        if not 0 <= level < self.numLevels():
+            raise ValueError(f"no level {level}")
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("a torch tensor is needed")
+        g = self.getLevel(level).geom
+        n = {"x": g.nx, "y": g.ny, "z": g.nz}
+        want = tuple(n[a] for a in order)
+        if tuple(t.shape) != want:
+            raise ValueError(f"shape {tuple(t.shape)}: level {level}'s interior in order {order!r} is {want}")
+        if t.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"dtype {t.dtype}: float32 or float64 is needed")
+        if not t.is_cuda or t.device.index != self.device_index:
+            raise ValueError(f"device {t.device}: the grid lives on cuda:{self.device_index}")
+        stride = (_abi.i64 * 3)(*(t.stride(order.index(a)) for a in "xyz"))
+        dtype = GS_IO_F32 if t.dtype == torch.float32 else GS_IO_F64
+        user = torch.cuda.current_stream(t.device).cuda_stream
+        return level, FIELDS[name], C.c_void_p(t.data_ptr()), dtype, stride, float(scale), C.c_void_p(user)
+
+    def load(self, name: str, tensor, level: int = 0, scale: float = 1.0, order: str = "zyx"):
+        """Field `name`'s interior on `level` = scale * tensor, on the device: no host copy, no synchronisation
+        (gs_grid_import of include/gpusolve_driver.h). `order` is a permutation of "xyz" naming the tensor's index
+        order — "zyx" is torch-natural ([z][y][x], x fastest), "xyz" is what field() returns — and the tensor's own
+        strides go through it: views, slices, permuted and expanded (stride 0) tensors need no .contiguous(). float32
+        or float64 on the grid's device, shaped as the level's interior in that order; ValueError otherwise, before any
+        call. Ordered after the work on torch.cuda.current_stream(); the tensor may be reused there straight away."""
+        _check(driver().gs_grid_import(self.handle, *self._io_call(name, tensor, level, scale, order)))
+
+    def store(self, name: str, out=None, level: int = 0, scale: float = 1.0, order: str = "zyx", dtype=None):
+        """out = scale * field `name`'s interior on `level`, on the device (gs_grid_export); returns `out`. Without
+        `out` a contiguous tensor in `order` of `dtype` (float64 without one) is made on the grid's device; with it,
+        its own strides are used (they must not make two points share an element) and `dtype`, if given, must be
+        its. Work enqueued on torch.cuda.current_stream() after the call sees the result; nothing is synchronised."""
+        import torch
+
+        if not isinstance(order, str) or sorted(order) != ["x", "y", "z"]:
+            raise ValueError('order must be a permutation of "xyz" naming the tensor\'s index order')
+        if not 0 <= level < self.numLevels():
+            raise ValueError(f"no level {level}")
+        if out is None:
+            g = self.getLevel(level).geom
+            n = {"x": g.nx, "y": g.ny, "z": g.nz}
+            dtype = torch.float64 if dtype is None else dtype
+            if dtype not in (torch.float32, torch.float64):
+                raise ValueError(f"dtype {dtype}: float32 or float64 is needed")
+            out = torch.empty(tuple(n[a] for a in order), dtype=dtype, device=f"cuda:{self.device_index}")
+        elif dtype is not None and isinstance(out, torch.Tensor) and out.dtype != dtype:
+            raise ValueError(f"dtype {dtype} asked for, but out is {out.dtype}")
+        _check(driver().gs_grid_export(self.handle, *self._io_call(name, out, level, scale, order)))
+        return out
 
     def sync(self):
         _check(driver().gs_grid_sync(self.handle))

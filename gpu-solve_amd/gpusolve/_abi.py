@@ -15,6 +15,7 @@ TRANSFER_LIB = os.path.join(LIB_DIR, "libgpusolve_transfer.so")  # position-awar
 KRYLOV_LIB = os.path.join(LIB_DIR, "libgpusolve_krylov.so")  # the PCG passes (include/gpusolve_krylov.h)
 LINE_LIB = os.path.join(LIB_DIR, "libgpusolve_line.so")  # the z-line smoother (include/gpusolve_line.h)
 SEMI_LIB = os.path.join(LIB_DIR, "libgpusolve_semi.so")  # XY semi-coarsening (include/gpusolve_semi.h)
+IO_LIB = os.path.join(LIB_DIR, "libgpusolve_io.so")  # device-side field import / export (include/gpusolve_io.h)
 DIAG_LIB = os.path.join(LIB_DIR, "libgpusolve_diag.so")  # tools/ and tests/ only (include/gpusolve_diag.h)
 DRIVER_LIB = os.path.join(LIB_DIR, "libgpusolve_driver.so")
 EXECUTABLE = os.path.join(BIN_DIR, "GpuSolve-hip")
@@ -34,6 +35,8 @@ GS_PCG_RZ_I, GS_PCG_PQ_I, GS_PCG_ALPHA_I, GS_PCG_BETA_I, GS_PCG_RR_I, GS_PCG_FLA
 GS_PCG_BAD_PQ, GS_PCG_BAD_RZ, GS_PCG_BAD_RR = 1, 2, 4
 GS_PCG_PQ, GS_PCG_RR, GS_PCG_RZ, GS_PCG_RZ_FIRST = 0, 1, 2, 3
 GS_PCG_BREAKDOWN = 2  # gs_grid_pcg's return code for a run that ended in a breakdown (include/gpusolve_driver.h)
+GS_IO_F64, GS_IO_F32 = 0, 1  # the external dtype of an import / export (include/gpusolve_io.h)
+GS_IO_IMPORT, GS_IO_EXPORT = 0, 1  # gs_io_kernel's dir
 GS_MAX_WEIGHTS = 8  # per-sweep relaxation weights per smoothing leg (include/gpusolve_hip.h)
 
 dptr = C.POINTER(C.c_double)
@@ -238,6 +241,17 @@ SEMI_API = {
     "gs_semi_launch_record": (i64, [C.c_char_p, i64]),
 }
 
+# libgpusolve_io.so (include/gpusolve_io.h): device-side field import / export — any strides, fp32 / fp64
+IO_API = {
+    "gs_io_import": (C.c_int, [C.c_void_p, C.POINTER(gs_level), C.c_void_p, C.c_int, C.POINTER(i64), C.c_double,
+                               C.c_void_p]),
+    "gs_io_export": (C.c_int, [C.c_void_p, C.POINTER(gs_level), C.c_void_p, C.c_int, C.POINTER(i64), C.c_double,
+                               C.c_void_p]),
+    "gs_io_kernel": (C.c_char_p, [C.c_int, C.c_int, C.POINTER(gs_level), C.POINTER(i64)]),
+    "gs_io_launch_dry_run": (C.c_int, [C.c_int]),
+    "gs_io_launch_record": (i64, [C.c_char_p, i64]),
+}
+
 DRIVER_API = {
     "gs_parse_config": (C.c_int, [C.c_char_p, C.POINTER(gs_params)]),
     "gs_grid_create": (C.c_void_p, [C.POINTER(gs_params)]),
@@ -275,6 +289,10 @@ DRIVER_API = {
     "gs_grid_stream": (C.c_void_p, [C.c_void_p]),
     "gs_grid_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dptr]),
     "gs_grid_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dptr]),
+    "gs_grid_import": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(i64), C.c_double,
+                                 C.c_void_p]),
+    "gs_grid_export": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(i64), C.c_double,
+                                 C.c_void_p]),
     "gs_grid_sync": (C.c_int, [C.c_void_p]),
     "gs_grid_comm_stats": (C.c_int, [C.c_void_p, dptr, C.POINTER(C.c_int64)]),
     "gs_grid_comm_stats_max": (C.c_int, [C.c_void_p, dptr]),
@@ -384,6 +402,12 @@ def semi():
     return _load(SEMI_LIB, SEMI_API)
 
 
+def io():
+    """The field import / export library (libgpusolve_io.so)."""
+    kernels()
+    return _load(IO_LIB, IO_API)
+
+
 def diag():
     """The diagnostics library (libgpusolve_diag.so): measurement and tuning code, never the product path."""
     kernels()
@@ -396,4 +420,5 @@ def driver():
     krylov()
     line()
     semi()
+    io()
     return _load(DRIVER_LIB, DRIVER_API)

@@ -230,6 +230,25 @@ hipStream_t gs_grid_stream(void* grid);
  * [nz+2][ny+2][nx+2] (x fastest). */
 int gs_grid_download(void* grid, int level, int field, double* host);
 int gs_grid_upload(void* grid, int level, int field, const double* host);
+/* Device-side import / export of a field's interior (added; include/gpusolve_io.h has the semantics: `dev` is a device
+ * array of dtype GS_IO_F64 / GS_IO_F32 addressed by three element strides, one per grid axis, scaled by `scale`; the
+ * arithmetic, the accepted strides and the instances are gs_io_import's / gs_io_export's). No host copy and no host
+ * synchronisation: the call returns with the work enqueued.
+ *   Field state: the field ids and the rules of gs_grid_upload / gs_grid_download — an imported v or f of a level is
+ *   what the next operation on that level reads, an import of newtonV invalidates what the driver derived from it, every
+ *   field is exported stored. Only interior points are written: the ring keeps its values (v's: the zero Dirichlet
+ *   value), so unlike an upload an import cannot set it.
+ *   Ordering: `user` is the stream on which the caller produced (import) or will consume (export) `dev`. The copy runs
+ *   on the grid's stream after everything enqueued on `user` so far, and work enqueued on `user` after the call runs
+ *   after the copy — two events per grid, in both directions, so `dev` may be overwritten or freed on `user` straight
+ *   away. With `user` the grid's own stream (gs_grid_stream) no event is used.
+ *   Refused (1, the reason in gs_last_error(), nothing touched): a Z-slab / RCCL or schedule-trace grid (a rank holds a
+ *   slab whose ghost planes would need an exchange), no such level or field, a null `dev`, and whatever gs_io_import /
+ *   gs_io_export answer with GS_EINVAL. */
+int gs_grid_import(void* grid, int level, int field, const void* dev, int dtype, const int64_t stride[3], double scale,
+                   hipStream_t user);
+int gs_grid_export(void* grid, int level, int field, void* dev, int dtype, const int64_t stride[3], double scale,
+                   hipStream_t user);
 int gs_grid_sync(void* grid);
 /* Host cost of the ghost exchanges issued so far (Z-slab grids): total wall milliseconds spent inside
  * the exchange calls (RCCL: group start/end and the settle poll of the non-blocking communicator) and
