@@ -67,7 +67,10 @@ void gs_grid_destroy(void* grid);
  * and their total count into *count.
  *
  * What a grid holds between calls (tests/session_ref.py is this rule as a CPU model, tests/test_gpu_sessions.py holds
- * the driver to it). Level 0's v (NEWTON: newtonV) and f are always the reference's. On the levels below:
+ * the driver to it; the model covers the operations declared below too — gs_grid_pcg, gs_grid_set_smoother, XY grids,
+ * gs_grid_set_fmg_prolong, gs_grid_import / gs_grid_export and the refusals "with nothing changed" — and
+ * tests/test_gpu_feature_sessions.py holds the driver to those in sequence). Level 0's v (NEWTON: newtonV) and f are
+ * always the reference's. On the levels below:
  *   - gs_grid_vcycle, gs_grid_fmg and a solve that ran all its cycles (or stopped on its last one) leave every level's
  *     v and f as that last V-cycle left them: f the restricted residual (FAS: + A(restV)), v the post-smoothed iterate.
  *     NONLINEAR: v is the FAS iterate itself; the reference overwrites it with the correction v - restV

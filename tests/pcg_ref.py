@@ -2,8 +2,8 @@
 tests/test_gpu_pcg.py (TEST INFRASTRUCTURE ONLY; the product never imports it).
 
 It is composed of what the driver composes on the device: M^-1 r is tests/xfer_ref.py's Cycle from a
-zero iterate with r as right-hand side (vcycle_from(0)), A u is the oracle's apply_op with gamma = 0, the initial
-residual the oracle's residual, and the updates are numpy expressions that round every product and sum once, as the
+zero iterate with r as right-hand side (vcycle_from(0)), A u is the oracle's LINEAR residual of a zero right-hand side,
+negated (apply_op with gamma = 0, bit for bit), the initial residual the oracle's residual, and the updates are numpy expressions that round every product and sum once, as the
 kernels do under -ffp-contract=off: p = z + beta * p, x = x + alpha * p, r = r - alpha * q. The dot products are
 math.fsum over the interior, i.e. exactly rounded: the device's fixed-order sums differ from them within the standard
 bound dot_bound().
@@ -39,8 +39,10 @@ def dot_bound(n, sum_abs):
 
 
 class Pcg:
-    def __init__(self, dims, f, x0=None, pre=(0.8, 0.8), post=(0.8, 0.8), transfer="position", stencil=None):
-        self.dims = tuple(dims)
+    def __init__(self, dims, f, x0=None, pre=(0.8, 0.8), post=(0.8, 0.8), transfer="position", stencil=None, cycle=None):
+        """cycle: a factory r -> a Cycle on right-hand side r with a zero iterate (its vcycle_from(0) and v[0] are
+        used); None: xfer_ref.Cycle with this object's pre, post, transfer and stencil."""
+        self.dims, self.cycle = tuple(dims), cycle
         self.pre, self.post, self.transfer, self.stencil = tuple(pre), tuple(post), transfer, stencil
         self.h = 1.0 / (self.dims[1] + 1)
         self.f = np.ascontiguousarray(f, dtype=np.float64)
@@ -49,12 +51,20 @@ class Pcg:
 
     def M(self, r):
         """One model V-cycle from the zero iterate on right-hand side r: the preconditioner."""
-        c = X.Cycle(self.dims, O.LINEAR, self.pre, self.post, f0=r, transfer=self.transfer, stencil=self.stencil)
+        if self.cycle is not None:
+            c = self.cycle(r)
+        else:
+            c = X.Cycle(self.dims, O.LINEAR, self.pre, self.post, f0=r, transfer=self.transfer, stencil=self.stencil)
         c.vcycle_from(0)
         return c.v[0]
 
     def A(self, u):
-        return O.apply_op(np.ascontiguousarray(u), self.h, 0.0, self.stencil)
+        """A u as 0 - (0 - A u) of the oracle's LINEAR residual: the same stencil sum and division as apply_op with
+        gamma = 0, bit for bit, without its 0 * u * exp(u), which is NaN where |u| is large enough for exp to overflow
+        (a preconditioned residual of an unscaled right-hand side is)."""
+        u = np.ascontiguousarray(u)
+        r, _ = O.residual(u, np.zeros_like(u), self.h, O.LINEAR, stencil=self.stencil)
+        return 0.0 - r
 
     def _start(self):
         self.r, _ = O.residual(self.x, self.f, self.h, O.LINEAR, stencil=self.stencil)

@@ -28,7 +28,8 @@ from conftest import rel  # noqa: E402
 # every switch the driver reads per grid (the kernel library's own knobs are read once per process: left alone)
 DRIVER_SWITCHES = S.SWITCHES + ("GS_TRANSFER", "GS_OMEGAS", "GS_FMG", "GS_NO_SWEEP3", "GS_METRICS", "GS_ZSLAB_MIN_POINTS",
                                 "GS_NO_NEWTON_FUSED_UPDATE", "GS_NO_NEWTON_B", "GS_NEWTON_B_FUSED", "GS_NO_NEWTON_G",
-                                "GS_NEWTON_PRO_POINTS", "GS_HALO_ORDER")
+                                "GS_NEWTON_PRO_POINTS", "GS_HALO_ORDER", "GS_SMOOTHER", "GS_COARSEN", "GS_SOLVER",
+                                "GS_FMG_PROLONG")
 MODES = {O.LINEAR: "LINEAR", O.NONLINEAR: "NONLINEAR", O.NEWTON: "NEWTON"}
 WORST = {m: dict(field=0.0, norm=0.0, seconds=0.0, slowest="") for m in MODES}  # filled as the sessions run
 SEEN = {}  # session index -> the regimes it reached
@@ -53,7 +54,7 @@ class GpuSession:
         p = gsv.GridParams(maxiter=case["maxiter"], tol=case["tol"], gridDim=case["dims"], mode=case["mode"],
                            preSmoothing=case["pre"], postSmoothing=case["post"], omega=case["omega"], gamma=case["gamma"],
                            stencil=gsv.Stencil(list(case["values"]), list(case["offsets"])))
-        self.g = gsv.HipGridData(p)
+        self.g = gsv.HipGridData(p, coarsen=case.get("coarsen"))  # (none: gs_grid_create, as every session here)
         self.cycle_triples = 0  # fused triples run inside solve / vcycle / vcycle_level / fmg
 
     def triples(self):
