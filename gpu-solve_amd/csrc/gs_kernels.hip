@@ -70,6 +70,65 @@ int launch_newton_upd(const gs_stencil* S, const gs_level* L, double gamma, cons
     return launch_status();
 }
 
+// gs_residual_restrict's LDS kernel k_resrestrict (the levels k_rr2 does not take): >= 4096 blocks where the level
+// has them, 1..16 coarse planes each
+struct RrPlan {
+    int zc;
+    dim3 grid;
+};
+RrPlan rr_lds_plan(const gs_level* cl)
+{
+    const int64_t tiles = ((cl->nx + RR_TXC - 1) / RR_TXC) * ((cl->ny + RR_TYC - 1) / RR_TYC);
+    int64_t zc = tiles * cl->nz / 4096;
+    zc = zc < 1 ? 1 : (zc > 16 ? 16 : zc);
+    return RrPlan{(int)zc, dim3((unsigned)((cl->nx + RR_TXC - 1) / RR_TXC), (unsigned)((cl->ny + RR_TYC - 1) / RR_TYC),
+                                (unsigned)((cl->nz + zc - 1) / zc))};
+}
+
+// gs_residual_restrict's checks of what is not a pointer (mode: a base mode)
+bool bad_rr_levels(const gs_stencil* S, const gs_level* fl, const gs_level* cl, int mode)
+{
+    return !S || !valid_stencil(S) || mode < GS_LINEAR || mode > GS_NEWTON_B || bad_level(fl) || bad_level(cl);
+}
+// the residual is evaluated on fine local planes 2z+zoff-1 .. 2z+zoff+1 of the interior only
+// (planes 0 and nz+1 hold r = 0): they must exist, as must the coarse points' fine columns
+bool bad_rr_planes(const gs_level* fl, const gs_level* cl)
+{
+    const int64_t zoff = 2 * cl->z0 - fl->z0; // fine local centre plane = 2 z + zoff
+    return 2 * cl->nx + 1 > fl->nx + 1 || 2 * cl->ny + 1 > fl->ny + 1 || 2 + zoff - 1 < 0 ||
+           2 * cl->nz + zoff + 1 > fl->nz + 1;
+}
+
+// k_rr2 takes this residual + restriction (else k_resrestrict): no GS_RR_LDS, canonical stencil order, coarse plane z
+// over fine plane 2 z, rows of at most RR2_WXMAX x-waves
+bool rr2_takes(const gs_stencil* S, const gs_level* fl, const gs_level* cl)
+{
+    const int64_t zoff = 2 * cl->z0 - fl->z0;
+    const int64_t wxs = ((fl->nx + 1) / 2 + WAVE - 1) / WAVE; // x-waves covering coarse columns 1..(fnx+1)/2
+    return !kKnobs.rrLds && canonical_order(S) && zoff == 0 && wxs <= RR2_WXMAX;
+}
+
+// gs_fmg_prolong's launch shape. Non-temporal fine stores for a stream larger than the Infinity Cache (GS_FMG_NT
+// forces either, A/B). z-cells per block: 8 on levels that do not fill the chip, else the chunk of 8..64 that makes
+// the grid whole rounds of resident blocks (fit_chunk; each chunk stages three planes more than it has cells)
+struct FpPlan {
+    bool nt;
+    int zc;
+    dim3 grid;
+};
+FpPlan fp_plan(const gs_level* cl, const gs_level* fl)
+{
+    const bool nt = kKnobs.fmgNt < 0 ? fl->nx * fl->ny * fl->nz >= ((int64_t)1 << 25) : kKnobs.fmgNt != 0;
+    const int64_t cells = cl->nz + 1;
+    const int64_t tiles = ((cl->nx + FP_TX) / FP_TX) * ((cl->ny + FP_TY) / FP_TY);
+    const auto fn = nt ? k_fmg_prolong<true> : k_fmg_prolong<false>;
+    int zc = fit_chunk(tiles, cells, resident_blocks((const void*)fn, FP_TX * FP_TY), 8, 64, false, 3.0);
+    if (zc < 8) zc = tiles >= 256 && cells >= 128 ? 32 : 8; // (GS_FIT_ROUNDS=0)
+    return FpPlan{nt, zc,
+                  dim3((unsigned)((cl->nx + FP_TX) / FP_TX), (unsigned)((cl->ny + FP_TY) / FP_TY),
+                       (unsigned)((cells + zc - 1) / zc))};
+}
+
 } // namespace
 
 // =============================================================================================
@@ -430,6 +489,13 @@ int gs_residual_restrict(const gs_stencil* S, const gs_level* fl, int mode, doub
     return gs_residual_restrict_slab(S, fl, mode, gamma, v, f, w, ca, cb, cl, 0, st);
 }
 
+int gs_residual_restrict_chunk(const gs_stencil* S, const gs_level* fl, const gs_level* cl, int mode)
+{
+    if (bad_rr_levels(S, fl, cl, base_mode(mode))) return 0;
+    if (cl->nx == 0 || cl->ny == 0 || cl->nz == 0 || bad_rr_planes(fl, cl)) return 0;
+    return rr2_takes(S, fl, cl) ? 0 : rr_lds_plan(cl).zc;
+}
+
 int gs_residual_restrict_slab_supported(const gs_stencil* S, const gs_level* fl)
 {
     const bool ldsOnly = kKnobs.rrLds;
@@ -443,20 +509,13 @@ int gs_residual_restrict_slab(const gs_stencil* S, const gs_level* fl, int mode,
 {
     const int bconst = mode == GS_NEWTON_G; // (Coef::bconst: k_rr2 takes gamma for the factor)
     mode = base_mode(mode);
-    if (!S || !valid_stencil(S) || !v || !f || !ca || (newtonish(mode) && !w) || mode < GS_LINEAR ||
-        mode > GS_NEWTON_B || bad_level(fl) || bad_level(cl))
-        return GS_EINVAL;
+    if (!v || !f || !ca || (newtonish(mode) && !w) || bad_rr_levels(S, fl, cl, mode)) return GS_EINVAL;
     if (cl->nx == 0 || cl->ny == 0 || cl->nz == 0) return 0;
+    if (bad_rr_planes(fl, cl)) return GS_EINVAL;
     const int64_t zoff = 2 * cl->z0 - fl->z0; // fine local centre plane = 2 z + zoff
-    // the residual is evaluated on fine local planes 2z+zoff-1 .. 2z+zoff+1 of the interior only
-    // (planes 0 and nz+1 hold r = 0): they must exist, as must the coarse points' fine columns
-    if (2 * cl->nx + 1 > fl->nx + 1 || 2 * cl->ny + 1 > fl->ny + 1 || 2 + zoff - 1 < 0 ||
-        2 * cl->nz + zoff + 1 > fl->nz + 1)
-        return GS_EINVAL;
     const Coef k = make_coef(S, fl, 0.0, gamma, bconst);
     const int64_t wxs = ((fl->nx + 1) / 2 + WAVE - 1) / WAVE; // x-waves covering coarse columns 1..(fnx+1)/2
-    const bool ldsOnly = kKnobs.rrLds; // A/B switch for tools/ measurements
-    const bool rr2 = !ldsOnly && canonical_order(S) && zoff == 0 && wxs <= RR2_WXMAX;
+    const bool rr2 = rr2_takes(S, fl, cl); // (GS_RR_LDS: A/B switch for tools/ measurements)
     if (zhi && !rr2) return GS_EINVAL; // the slab form exists for the register kernel only
     if (rr2) {
         // >= 2048 blocks of one coarse row where the level has them (chunks of <= 32 coarse planes)
@@ -493,11 +552,9 @@ int gs_residual_restrict_slab(const gs_stencil* S, const gs_level* fl, int mode,
         so.lds[t] = S->ox[t] + S->oy[t] * RR_VX;
         so.oz[t] = S->oz[t];
     }
-    const int64_t tiles = ((cl->nx + RR_TXC - 1) / RR_TXC) * ((cl->ny + RR_TYC - 1) / RR_TYC);
-    int64_t zc = tiles * cl->nz / 4096; // >= 4096 blocks where the level has them, 1..16 planes each
-    zc = zc < 1 ? 1 : (zc > 16 ? 16 : zc);
-    const dim3 g((unsigned)((cl->nx + RR_TXC - 1) / RR_TXC), (unsigned)((cl->ny + RR_TYC - 1) / RR_TYC),
-                 (unsigned)((cl->nz + zc - 1) / zc));
+    const RrPlan plan = rr_lds_plan(cl);
+    const int zc = plan.zc;
+    const dim3 g = plan.grid;
     with_mode([&](auto M) {
         launch(k_resrestrict<M>, g, dim3(RR_T), st, k, so, v, f, w, ca, cb, (int)fl->nx, (int)fl->ny,
                            (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy, cl->ldz,
@@ -546,21 +603,20 @@ int gs_fmg_prolong_supported(const gs_level* cl, const gs_level* fl)
                : 0;
 }
 
+int gs_fmg_prolong_chunk(const gs_level* cl, const gs_level* fl)
+{
+    if (!gs_fmg_prolong_supported(cl, fl)) return 0;
+    const FpPlan plan = fp_plan(cl, fl);
+    return plan.grid.y > 65535u || plan.grid.z > 65535u ? 0 : plan.zc;
+}
+
 int gs_fmg_prolong(const double* coarse, const gs_level* cl, double* fine, const gs_level* fl, hipStream_t st)
 {
     if (!coarse || !fine || !gs_fmg_prolong_supported(cl, fl)) return GS_EINVAL;
-    // non-temporal fine stores for a stream larger than the Infinity Cache (GS_FMG_NT forces either, A/B)
-    const bool nt = kKnobs.fmgNt < 0 ? fl->nx * fl->ny * fl->nz >= ((int64_t)1 << 25) : kKnobs.fmgNt != 0;
-    // z-cells per block: 8 on levels that do not fill the chip, else the chunk of 8..64 that makes the grid whole
-    // rounds of resident blocks (fit_chunk; each chunk stages three planes more than it has cells)
-    const int64_t cells = cl->nz + 1;
-    const int64_t tiles = ((cl->nx + FP_TX) / FP_TX) * ((cl->ny + FP_TY) / FP_TY);
-    const auto fn = nt ? k_fmg_prolong<true> : k_fmg_prolong<false>;
-    int zc = fit_chunk(tiles, cells, resident_blocks((const void*)fn, FP_TX * FP_TY), 8, 64, false, 3.0);
-    if (zc < 8) zc = tiles >= 256 && cells >= 128 ? 32 : 8; // (GS_FIT_ROUNDS=0)
-    const dim3 g((unsigned)((cl->nx + FP_TX) / FP_TX), (unsigned)((cl->ny + FP_TY) / FP_TY),
-                 (unsigned)((cells + zc - 1) / zc)),
-        b(FP_TX, FP_TY);
+    const FpPlan plan = fp_plan(cl, fl);
+    const auto fn = plan.nt ? k_fmg_prolong<true> : k_fmg_prolong<false>;
+    const int zc = plan.zc;
+    const dim3 g = plan.grid, b(FP_TX, FP_TY);
     if (g.y > 65535u || g.z > 65535u) return GS_EINVAL;
     // the fine pair (2i+1, 2i+2) as one 16-byte store where the layout aligns it (gs_field_layout does)
     const int al = ((reinterpret_cast<uintptr_t>(fine + 1) & 15) == 0 && fl->ldy % 2 == 0 && fl->ldz % 2 == 0) ? 1 : 0;

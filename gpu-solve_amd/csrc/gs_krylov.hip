@@ -112,6 +112,13 @@ int gs_pcg_step(const gs_level* L, double* x, double* r, const double* p, const 
 
 int64_t gs_dot_num_partials(const gs_level* L) { return gs_pcg_step_num_partials(L); }
 
+int gs_krylov_vec_chunk(const gs_level* L)
+{
+    if (bad_krylov_level(L) || empty_level(L)) return 0;
+    const VecPlan plan = vec_plan(L);
+    return bad_grid(plan.grid) ? 0 : plan.zc;
+}
+
 int gs_dot(const gs_level* L, const double* a, const double* b, double* partials, hipStream_t st)
 {
     if (bad_krylov_level(L) || !a || !b || !partials) return GS_EINVAL;

@@ -38,17 +38,39 @@ bool semi_shape(const gs_stencil* S, SemiShape* out)
 
 // whole levels, fine (nx, ny, nz) -> coarse (nx / 2, ny / 2, nz), tables for exactly that; one block per plane in
 // the grid's z extent (the two stored-field kernels) and per XY_TYC / 4 rows in its y extent
+bool bad_xy_pair(const gs_level* fl, const gs_level* cl)
+{
+    if (bad_level(fl) || bad_level(cl) || fl->z0 != 0 || cl->z0 != 0) return true;
+    if (fl->nx < 2 || fl->ny < 2 || cl->nx != fl->nx / 2 || cl->ny != fl->ny / 2 || cl->nz != fl->nz) return true;
+    return fl->nz > 65535 || (fl->ny + 3) / 4 > 65535;
+}
+
 bool bad_xy(const gs_level* fl, const gs_level* cl, const gs_transfer_tables* T)
 {
-    if (bad_level(fl) || bad_level(cl) || !T || fl->z0 != 0 || cl->z0 != 0) return true;
+    if (bad_xy_pair(fl, cl) || !T) return true;
     const int64_t nf[2] = {fl->nx, fl->ny}, nc[2] = {cl->nx, cl->ny};
     for (int a = 0; a < 2; a++) {
-        if (nf[a] < 2 || nc[a] != nf[a] / 2 || T->nf[a] != nf[a] || T->nc[a] != nc[a]) return true;
+        if (T->nf[a] != nf[a] || T->nc[a] != nc[a]) return true;
         if (!T->pj[a] || !T->pt[a] || !T->rlo[a] || !T->rcnt[a] || !T->rw[a]) return true;
     }
-    if (cl->nz != fl->nz || T->nf[2] != fl->nz || T->nc[2] != fl->nz) return true;
+    if (T->nf[2] != fl->nz || T->nc[2] != fl->nz) return true;
     if (T->pj[2] || T->pt[2] || T->rlo[2] || T->rcnt[2] || T->rw[2]) return true;
-    return fl->nz > 65535 || (fl->ny + 3) / 4 > 65535;
+    return false;
+}
+
+// gs_residual_restrict_xy's launch shape: z-chunks of 8..64 planes (a chunk re-reads two v planes), for ~2048 blocks
+// where the level has them
+struct XyPlan {
+    int zc;
+    dim3 grid;
+};
+XyPlan xy_plan(const gs_level* fl, const gs_level* cl)
+{
+    const int64_t tiles = ((cl->nx + XY_TXC - 1) / XY_TXC) * ((cl->ny + XY_TYC - 1) / XY_TYC);
+    int64_t zc = fl->nz * tiles / 2048;
+    zc = zc < 8 ? 8 : (zc > 64 ? 64 : zc);
+    return XyPlan{(int)zc, dim3((unsigned)((cl->nx + XY_TXC - 1) / XY_TXC), (unsigned)((cl->ny + XY_TYC - 1) / XY_TYC),
+                                (unsigned)((fl->nz + zc - 1) / zc))};
 }
 
 XyTables device_tables(const gs_transfer_tables* T)
@@ -121,16 +143,18 @@ int gs_residual_restrict_xy(const gs_stencil* S, const gs_level* fl, const doubl
         so.lds[t] = S->ox[t] + S->oy[t] * XY_VX;
         so.oz[t] = S->oz[t];
     }
-    // z-chunks of 8..64 planes (a chunk re-reads two v planes), for ~2048 blocks where the level has them
-    const int64_t tiles = ((cl->nx + XY_TXC - 1) / XY_TXC) * ((cl->ny + XY_TYC - 1) / XY_TYC);
-    int64_t zc = fl->nz * tiles / 2048;
-    zc = zc < 8 ? 8 : (zc > 64 ? 64 : zc);
-    const dim3 g((unsigned)((cl->nx + XY_TXC - 1) / XY_TXC), (unsigned)((cl->ny + XY_TYC - 1) / XY_TYC),
-                 (unsigned)((fl->nz + zc - 1) / zc)),
-        b(XY_T);
+    const XyPlan plan = xy_plan(fl, cl);
+    const int zc = plan.zc;
+    const dim3 g = plan.grid, b(XY_T);
     launch(k_resrestrict_xy, g, b, st, k, so, device_tables(T), v, f, coarse_f, (int)fl->nx, (int)fl->ny, (int)fl->nz,
            fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, cl->ldy, cl->ldz, (int)zc);
     return launch_status();
+}
+
+int gs_residual_restrict_xy_chunk(const gs_level* fl, const gs_level* cl)
+{
+    if (bad_xy_pair(fl, cl) || fl->nz == 0) return 0;
+    return xy_plan(fl, cl).zc;
 }
 
 const char* gs_semi_kernel(int op, const gs_level* fl, const gs_level* cl)

@@ -8,16 +8,28 @@
 
 namespace {
 
+// whole levels, coarse = fine / 2 per axis
+bool bad_pair(const gs_level* fl, const gs_level* cl)
+{
+    if (bad_level(fl) || bad_level(cl) || fl->z0 != 0 || cl->z0 != 0) return true;
+    const int64_t nf[3] = {fl->nx, fl->ny, fl->nz}, nc[3] = {cl->nx, cl->ny, cl->nz};
+    for (int a = 0; a < 3; a++)
+        if (nf[a] < 2 || nc[a] != nf[a] / 2) return true;
+    return false;
+}
+
+// one block per plane (transfers) / per PA_TYC coarse rows: the grid's y and z extents
+bool bad_pa_grid(const gs_level* fl) { return fl->nz > 65535 || (fl->ny + 3) / 4 > 65535; }
+
 bool bad_transfer(const gs_level* fl, const gs_level* cl, const gs_transfer_tables* T)
 {
-    if (bad_level(fl) || bad_level(cl) || !T || fl->z0 != 0 || cl->z0 != 0) return true;
+    if (bad_pair(fl, cl) || !T) return true;
     const int64_t nf[3] = {fl->nx, fl->ny, fl->nz}, nc[3] = {cl->nx, cl->ny, cl->nz};
     for (int a = 0; a < 3; a++) {
-        if (nf[a] < 2 || nc[a] != nf[a] / 2 || T->nf[a] != nf[a] || T->nc[a] != nc[a]) return true;
+        if (T->nf[a] != nf[a] || T->nc[a] != nc[a]) return true;
         if (!T->pj[a] || !T->pt[a] || !T->rlo[a] || !T->rcnt[a] || !T->rw[a]) return true;
     }
-    // one block per plane (transfers) / per PA_TYC coarse rows: the grid's y and z extents
-    return fl->nz > 65535 || (fl->ny + 3) / 4 > 65535;
+    return bad_pa_grid(fl);
 }
 
 PaTables device_tables(const gs_transfer_tables* T)
@@ -33,16 +45,53 @@ PaTables device_tables(const gs_transfer_tables* T)
     return d;
 }
 
+// (the kernel's 32-bit offsets inside a staged tile)
+bool bad_fmg_pair(const gs_level* fl, const gs_level* cl) { return bad_pair(fl, cl) || cl->ldy > INT32_MAX / 16; }
+
 bool bad_fmg_transfer(const gs_level* fl, const gs_level* cl, const gs_fmg_tables* T)
 {
-    if (bad_level(fl) || bad_level(cl) || !T || fl->z0 != 0 || cl->z0 != 0) return true;
+    if (bad_fmg_pair(fl, cl) || !T) return true;
     const int64_t nf[3] = {fl->nx, fl->ny, fl->nz}, nc[3] = {cl->nx, cl->ny, cl->nz};
     for (int a = 0; a < 3; a++) {
-        if (nf[a] < 2 || nc[a] != nf[a] / 2 || T->nf[a] != nf[a] || T->nc[a] != nc[a]) return true;
+        if (T->nf[a] != nf[a] || T->nc[a] != nc[a]) return true;
         if (!T->cj[a] || !T->cw[a]) return true;
     }
-    if (cl->ldy > INT32_MAX / 16) return true; // (the kernel's 32-bit offsets inside a staged tile)
     return false;
+}
+
+// gs_fmg_prolong_pa's launch shape. Non-temporal fine stores for a stream larger than the Infinity Cache, as
+// gs_fmg_prolong (GS_FMG_NT: A/B). Fine planes per block: 16 on levels that do not fill the chip, else the even chunk
+// of 16..128 that makes the grid whole rounds of resident blocks (fit_chunk; a chunk stages about three coarse
+// planes, six fine ones, more than it covers)
+struct FqPlan {
+    bool nt;
+    int zc;
+    dim3 grid;
+};
+FqPlan fq_plan(const gs_level* fl)
+{
+    const bool nt = kKnobs.fmgNt < 0 ? fl->nx * fl->ny * fl->nz >= ((int64_t)1 << 25) : kKnobs.fmgNt != 0;
+    const int64_t tiles = ((fl->nx + 2 * FQ_TX - 1) / (2 * FQ_TX)) * ((fl->ny + 2 * FQ_TY - 1) / (2 * FQ_TY));
+    const auto fn = nt ? k_fmg_prolong_pa<true> : k_fmg_prolong_pa<false>;
+    int zc = fit_chunk(tiles, fl->nz, resident_blocks((const void*)fn, FQ_T), 16, 128, true, 6.0);
+    if (zc < 16) zc = tiles >= 256 && fl->nz >= 256 ? 64 : 16; // (GS_FIT_ROUNDS=0)
+    return FqPlan{nt, zc,
+                  dim3((unsigned)((fl->nx + 2 * FQ_TX - 1) / (2 * FQ_TX)),
+                       (unsigned)((fl->ny + 2 * FQ_TY - 1) / (2 * FQ_TY)), (unsigned)((fl->nz + zc - 1) / zc))};
+}
+
+// gs_residual_restrict_pa's: z-chunks of 4..32 coarse planes, for ~1024 blocks where the level has them
+struct PaPlan {
+    int zc;
+    dim3 grid;
+};
+PaPlan pa_plan(const gs_level* cl)
+{
+    const int64_t tiles = ((cl->nx + PA_TXC - 1) / PA_TXC) * ((cl->ny + PA_TYC - 1) / PA_TYC);
+    int64_t zc = cl->nz * tiles / 1024;
+    zc = zc < 4 ? 4 : (zc > 32 ? 32 : zc);
+    return PaPlan{(int)zc, dim3((unsigned)((cl->nx + PA_TXC - 1) / PA_TXC), (unsigned)((cl->ny + PA_TYC - 1) / PA_TYC),
+                                (unsigned)((cl->nz + zc - 1) / zc))};
 }
 
 } // namespace
@@ -112,18 +161,10 @@ int gs_fmg_prolong_pa(const double* coarse, const gs_level* cl, double* fine, co
                       const gs_fmg_tables* T, hipStream_t st)
 {
     if (!coarse || !fine || bad_fmg_transfer(fl, cl, T)) return GS_EINVAL;
-    // non-temporal fine stores for a stream larger than the Infinity Cache, as gs_fmg_prolong (GS_FMG_NT: A/B)
-    const bool nt = kKnobs.fmgNt < 0 ? fl->nx * fl->ny * fl->nz >= ((int64_t)1 << 25) : kKnobs.fmgNt != 0;
-    // fine planes per block: 16 on levels that do not fill the chip, else the even chunk of 16..128 that makes the
-    // grid whole rounds of resident blocks (fit_chunk; a chunk stages about three coarse planes, six fine ones, more
-    // than it covers)
-    const int64_t tiles = ((fl->nx + 2 * FQ_TX - 1) / (2 * FQ_TX)) * ((fl->ny + 2 * FQ_TY - 1) / (2 * FQ_TY));
-    const auto fn = nt ? k_fmg_prolong_pa<true> : k_fmg_prolong_pa<false>;
-    int zc = fit_chunk(tiles, fl->nz, resident_blocks((const void*)fn, FQ_T), 16, 128, true, 6.0);
-    if (zc < 16) zc = tiles >= 256 && fl->nz >= 256 ? 64 : 16; // (GS_FIT_ROUNDS=0)
-    const dim3 g((unsigned)((fl->nx + 2 * FQ_TX - 1) / (2 * FQ_TX)), (unsigned)((fl->ny + 2 * FQ_TY - 1) / (2 * FQ_TY)),
-                 (unsigned)((fl->nz + zc - 1) / zc)),
-        b(FQ_TX, FQ_TY);
+    const FqPlan plan = fq_plan(fl);
+    const auto fn = plan.nt ? k_fmg_prolong_pa<true> : k_fmg_prolong_pa<false>;
+    const int zc = plan.zc;
+    const dim3 g = plan.grid, b(FQ_TX, FQ_TY);
     if (g.y > 65535u || g.z > 65535u) return GS_EINVAL;
     FqTables d;
     for (int a = 0; a < 3; a++) {
@@ -173,19 +214,28 @@ int gs_residual_restrict_pa(const gs_stencil* S, const gs_level* fl, int mode, d
         so.lds[t] = S->ox[t] + S->oy[t] * PA_VX;
         so.oz[t] = S->oz[t];
     }
-    // z-chunks of 4..32 coarse planes, for ~1024 blocks where the level has them
-    const int64_t tiles = ((cl->nx + PA_TXC - 1) / PA_TXC) * ((cl->ny + PA_TYC - 1) / PA_TYC);
-    int64_t zc = cl->nz * tiles / 1024;
-    zc = zc < 4 ? 4 : (zc > 32 ? 32 : zc);
-    const dim3 g((unsigned)((cl->nx + PA_TXC - 1) / PA_TXC), (unsigned)((cl->ny + PA_TYC - 1) / PA_TYC),
-                 (unsigned)((cl->nz + zc - 1) / zc)),
-        b(PA_T);
+    const PaPlan plan = pa_plan(cl);
+    const int zc = plan.zc;
+    const dim3 g = plan.grid, b(PA_T);
     with_mode([&](auto M) {
         launch(k_resrestrict_pa<M>, g, b, st, k, so, device_tables(T), v, f, w, coarse_f, (int)fl->nx,
                            (int)fl->ny, (int)fl->nz, fl->ldy, fl->ldz, (int)cl->nx, (int)cl->ny, (int)cl->nz, cl->ldy,
                            cl->ldz, (int)zc);
     }, mode);
     return launch_status();
+}
+
+int gs_residual_restrict_pa_chunk(const gs_level* fl, const gs_level* cl)
+{
+    if (bad_pair(fl, cl) || bad_pa_grid(fl)) return 0;
+    return pa_plan(cl).zc;
+}
+
+int gs_fmg_prolong_pa_chunk(const gs_level* fl, const gs_level* cl)
+{
+    if (bad_fmg_pair(fl, cl)) return 0;
+    const FqPlan plan = fq_plan(fl);
+    return plan.grid.y > 65535u || plan.grid.z > 65535u ? 0 : plan.zc;
 }
 
 int gs_transfer_launch_dry_run(int on) { return launch_dry_run(on); }

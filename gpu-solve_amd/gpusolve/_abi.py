@@ -115,6 +115,7 @@ KERNEL_API = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(gs_level), C.c_void_p]),
     "gs_residual_restrict_slab_supported": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level)]),
+    "gs_residual_restrict_chunk": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.POINTER(gs_level), C.c_int]),
     "gs_residual_restrict_slab": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int, C.c_double,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(gs_level), C.c_int, C.c_void_p]),
@@ -132,6 +133,7 @@ KERNEL_API = {
                                  C.c_void_p]),
     "gs_fmg_prolong_supported": (C.c_int, [C.POINTER(gs_level), C.POINTER(gs_level)]),
     "gs_fmg_prolong": (C.c_int, [C.c_void_p, C.POINTER(gs_level), C.c_void_p, C.POINTER(gs_level), C.c_void_p]),
+    "gs_fmg_prolong_chunk": (C.c_int, [C.POINTER(gs_level), C.POINTER(gs_level)]),
     "gs_apply_op": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_double, C.c_void_p, C.c_void_p,
                               C.c_void_p]),
     "gs_apply_op_add": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_double, C.c_void_p, C.c_void_p,
@@ -197,9 +199,11 @@ TRANSFER_API = {
     "gs_residual_restrict_pa": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_int, C.c_double, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(gs_level),
                                           C.POINTER(gs_transfer_tables), C.c_void_p]),
+    "gs_residual_restrict_pa_chunk": (C.c_int, [C.POINTER(gs_level), C.POINTER(gs_level)]),
     "gs_fmg_axis": (C.c_int, [i64, i64, C.POINTER(C.c_int32), dptr]),
     "gs_fmg_prolong_pa": (C.c_int, [C.c_void_p, C.POINTER(gs_level), C.c_void_p, C.POINTER(gs_level),
                                     C.POINTER(gs_fmg_tables), C.c_void_p]),
+    "gs_fmg_prolong_pa_chunk": (C.c_int, [C.POINTER(gs_level), C.POINTER(gs_level)]),
     "gs_transfer_launch_dry_run": (C.c_int, [C.c_int]),
     "gs_transfer_launch_record": (i64, [C.c_char_p, i64]),
 }
@@ -215,6 +219,7 @@ KRYLOV_API = {
     "gs_pcg_step_num_partials": (i64, [C.POINTER(gs_level)]),
     "gs_dot": (C.c_int, [C.POINTER(gs_level), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gs_dot_num_partials": (i64, [C.POINTER(gs_level)]),
+    "gs_krylov_vec_chunk": (C.c_int, [C.POINTER(gs_level)]),
     "gs_pcg_scalars": (C.c_int, [C.c_int, C.c_void_p, i64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
@@ -236,6 +241,7 @@ SEMI_API = {
                                     C.POINTER(gs_transfer_tables), C.c_void_p]),
     "gs_residual_restrict_xy": (C.c_int, [C.POINTER(gs_stencil), C.POINTER(gs_level), C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.POINTER(gs_level), C.POINTER(gs_transfer_tables), C.c_void_p]),
+    "gs_residual_restrict_xy_chunk": (C.c_int, [C.POINTER(gs_level), C.POINTER(gs_level)]),
     "gs_semi_kernel": (C.c_char_p, [C.c_int, C.POINTER(gs_level), C.POINTER(gs_level)]),
     "gs_semi_launch_dry_run": (C.c_int, [C.c_int]),
     "gs_semi_launch_record": (i64, [C.c_char_p, i64]),

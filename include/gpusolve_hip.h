@@ -218,6 +218,13 @@ int gs_sumsq_finish(const double* partials, int64_t n, double* out, int accumula
 int gs_residual_restrict(const gs_stencil* S, const gs_level* fine, int mode, double gamma, const double* v,
                          const double* f, const double* w, double* coarse_a, double* coarse_b,
                          const gs_level* coarse, hipStream_t stream);
+/* The z-chunk of gs_residual_restrict's LDS kernel (k_resrestrict: a stencil out of canonical order, rows of more
+ * than 1024 points, a coarse plane z that does not sit over fine plane 2z, GS_RR_LDS) on (S, fine, coarse, mode):
+ * COARSE planes per block, 1..16, from the plan function the launcher takes its grid from (block z index b covers
+ * coarse planes b * chunk + 1 .. min(cnz, (b + 1) * chunk)). 0 where the call takes the register kernel k_rr2 (its
+ * chunks have switches: GS_RR_ZC, GS_RR_ZC_BIG), for arguments the launcher refuses and for an empty coarse level.
+ * Launches nothing and needs no device. */
+int gs_residual_restrict_chunk(const gs_stencil* S, const gs_level* fine, const gs_level* coarse, int mode);
 /* The same on a Z-slab whose top (plane fine->nz + 1) is an internal boundary when zhi != 0: the
  * residual on that ghost plane is evaluated from the current ghost planes nz+1 of v, f, w and nz+2
  * of v instead of being the zero of a level boundary. Coarse plane z must sit over fine plane 2z
@@ -255,6 +262,12 @@ int gs_prolong_add(const double* coarse_v, const double* coarse_sub, const gs_le
  * outside the padded coarse array. */
 int gs_fmg_prolong_supported(const gs_level* coarse, const gs_level* fine);
 int gs_fmg_prolong(const double* coarse, const gs_level* cl, double* fine, const gs_level* fl, hipStream_t stream);
+/* The z-chunk gs_fmg_prolong launches with on (cl, fl): z-cells per block, 8..64, from the plan function the launcher
+ * takes its grid from. The cnz + 1 cells are the intervals between padded coarse planes: cell c, 0 <= c <= cnz, holds
+ * fine planes 2c + 1 and (but for the last) 2c + 2. Above 8 only where the level's blocks at 8 cells fill the device,
+ * and then the device's choice (the kernel's occupancy x its compute units; without a device 256 units of one block
+ * each are assumed). Launches nothing; 0 for levels the launcher refuses. */
+int gs_fmg_prolong_chunk(const gs_level* cl, const gs_level* fl);
 
 /* out = A(u)/h^2 + gamma*u*exp(u) on the interior (FAS coarse operator). */
 int gs_apply_op(const gs_stencil* S, const gs_level* L, double gamma, const double* u, double* out,

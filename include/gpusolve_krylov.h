@@ -68,6 +68,12 @@ int64_t gs_pcg_step_num_partials(const gs_level* L);
 int gs_dot(const gs_level* L, const double* a, const double* b, double* partials, hipStream_t stream);
 int64_t gs_dot_num_partials(const gs_level* L);
 
+/* The z-chunk gs_pcg_step and gs_dot launch with on L: planes per block, 1..16, from the plan function the two
+ * launchers take their grid from. Block (bx, by, bz) covers planes bz * chunk + 1 .. min(nz, (bz + 1) * chunk) and
+ * writes partials[(bz * gy + by) * gx + bx]. Launches nothing and needs no device; 0 for a level they refuse or an
+ * empty one. */
+int gs_krylov_vec_chunk(const gs_level* L);
+
 /* One block: s = the sum of partials[0 .. n-1] (n >= 0), then the update of `rec` (GS_PCG_REC doubles of device
  * memory) that `what` names. Quotients are IEEE divisions. A sum that decides a quotient (p . q, r . z) must be a
  * positive finite number: otherwise, or once the flag is set, the quotient is stored as 0 and the sum's flag bit is

@@ -63,6 +63,10 @@ int gs_prolong_add_xy(const double* coarse_v, const gs_level* cl, double* fine_v
  * followed by gs_restrict_xy. S: any stencil gs_residual takes. v's ring is read (it holds zeros), f's is not. */
 int gs_residual_restrict_xy(const gs_stencil* S, const gs_level* fl, const double* v, const double* f,
                             double* coarse_f, const gs_level* cl, const gs_transfer_tables* T, hipStream_t stream);
+/* The z-chunk gs_residual_restrict_xy launches with on (fl, cl): planes per block, 8..64, from the plan function the
+ * launcher takes its grid from (block z index b covers planes b * chunk + 1 .. min(nz, (b + 1) * chunk)). Launches
+ * nothing and needs no device; 0 for levels the launcher refuses and for nz = 0. */
+int gs_residual_restrict_xy_chunk(const gs_level* fl, const gs_level* cl);
 
 /* The kernel a launcher enqueues for (fl, cl): each has one instance, for every shape.
  *   GS_SEMI_RESIDUAL_RESTRICT  "k_resrestrict_xy"  a block owns 64 x 4 coarse columns and marches a chunk of planes:

@@ -72,6 +72,10 @@ int gs_prolong_add_pa(const double* coarse_v, const double* coarse_sub, const gs
 int gs_residual_restrict_pa(const gs_stencil* S, const gs_level* fl, int mode, double gamma, const double* v,
                             const double* f, const double* w, double* coarse_f, const gs_level* cl,
                             const gs_transfer_tables* T, hipStream_t stream);
+/* The z-chunk gs_residual_restrict_pa launches with on (fl, cl): COARSE planes per block, 4..32, from the plan
+ * function the launcher takes its grid from (block z index b covers coarse planes b * chunk + 1 ..
+ * min(cnz, (b + 1) * chunk)). Launches nothing and needs no device; 0 for levels the launcher refuses. */
+int gs_residual_restrict_pa_chunk(const gs_level* fl, const gs_level* cl);
 
 /* ---- Full multigrid's prolongation of a SOLUTION by position (gs_fmg_prolong's role on transitions that are not
  * aligned). Tricubic, separable, X then Y then Z. Per axis, with q, pj, rem, D as above and
@@ -102,6 +106,11 @@ int gs_fmg_axis(int64_t nf, int64_t nc, int32_t* cj, double* cw);
  * The launchers' conventions and layout contract above. */
 int gs_fmg_prolong_pa(const double* coarse, const gs_level* cl, double* fine, const gs_level* fl,
                       const gs_fmg_tables* T, hipStream_t stream);
+/* The z-chunk gs_fmg_prolong_pa launches with on (fl, cl): FINE planes per block, an even number in 16..128, from the
+ * plan function the launcher takes its grid from. Above 16 only where the level's blocks at 16 planes fill the
+ * device, and then the device's choice (the kernel's occupancy x its compute units; without a device 256 units of
+ * one block each are assumed). Launches nothing; 0 for levels the launcher refuses. */
+int gs_fmg_prolong_pa_chunk(const gs_level* fl, const gs_level* cl);
 
 /* This library's launch record: gs_launch_dry_run / gs_launch_record of include/gpusolve_hip.h for the launchers
  * above (each library keeps its own record and its own dry-run flag). */

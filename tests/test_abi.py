@@ -81,6 +81,10 @@ def test_python_binding_covers_headers():
     assert names <= exported(gsv._abi.TRANSFER_LIB)
     assert {"gs_launch_dry_run", "gs_launch_record"} <= set(gsv._abi.KERNEL_API)
     assert {"gs_transfer_launch_dry_run", "gs_transfer_launch_record"} <= names
+    # the chunk queries (tests/test_chunks_cpu.py): what a launcher's plan function gives, without a launch
+    assert {"gs_residual_restrict_pa_chunk", "gs_fmg_prolong_pa_chunk"} <= names
+    assert {"gs_fmg_prolong_chunk", "gs_residual_restrict_chunk"} <= set(gsv._abi.KERNEL_API)
+    assert {n for n in exported(gsv._abi.TRANSFER_LIB) if n.startswith("gs_")} == names
 
 
 def test_libraries_load_without_gpu():

@@ -48,15 +48,56 @@ def cases(n=None, seed=None):
     return out
 
 
-@pytest.mark.parametrize("case", cases(), ids=lambda c: f"c{c[0]}-{'x'.join(map(str, c[1]))}-m{c[2]}-{c[3]}+{c[4]}")
-def test_random_solve_vs_oracle(case):
+def siblings(drawn):
+    """For every drawn non-LINEAR case whose x or z axis is longer than y, the same case with its longest axis swapped
+    into y (x before z on a tie). The non-linear right-hand side is a function of x = i h with h = 1 / (ny + 1): where
+    ny is a short axis x runs far past 1, the oracle overflows and the drawn case compares few points or none; with
+    the longest axis in y every coordinate stays inside (0, 1]. A fixed rule: the oracle is not consulted."""
+    out = []
+    for i, dims, mode, *rest in drawn:
+        if mode != 0 and max(dims[0], dims[2]) > dims[1]:
+            a = 0 if dims[0] >= dims[2] else 2
+            d = list(dims)
+            d[a], d[1] = d[1], d[a]
+            out.append((f"{i}y", tuple(d), mode, *rest))
+    return out
+
+
+def case_id(c):
+    return f"c{c[0]}-{'x'.join(map(str, c[1]))}-m{c[2]}-{c[3]}+{c[4]}"
+
+
+MAXITER = 2
+
+
+def oracle_solve(case):
+    """(history, level 0's result) of the CPU oracle."""
     _, dims, mode, pre, post, omega, gamma, values, offsets = case
-    maxiter = 2
-    og = O.Grid(dims, mode=mode, maxiter=maxiter, omega=omega, gamma=gamma, pre=pre, post=post,
+    og = O.Grid(dims, mode=mode, maxiter=MAXITER, omega=omega, gamma=gamma, pre=pre, post=post,
                 stencil=O.Stencil.make(values, offsets))
     oh = og.solve()
+    return oh, og.field(0, "newtonV" if mode == 2 else "v").copy()
+
+
+@pytest.mark.parametrize("case", cases(), ids=case_id)
+def test_random_solve_vs_oracle(case):
+    solve_vs_oracle(case, finite=False)
+
+
+@pytest.mark.parametrize("case", siblings(cases()), ids=case_id)
+def test_sibling_solve_vs_oracle(case):
+    """No case that compares nothing: the siblings' oracle results are wholly finite, asserted before the comparison
+    (tests/test_fuzz_cases_cpu.py holds the whole draw to that without a GPU)."""
+    solve_vs_oracle(case, finite=True)
+
+
+def solve_vs_oracle(case, finite):
+    _, dims, mode, pre, post, omega, gamma, values, offsets = case
+    maxiter = MAXITER
+    oh, ref = oracle_solve(case)
+    if finite:
+        assert np.isfinite(ref).all() and np.isfinite(oh).all(), "the oracle's result is not finite"
     name = "newtonV" if mode == 2 else "v"
-    ref = og.field(0, name).copy()
     p = gsv.GridParams(maxiter=maxiter, tol=0.0, gridDim=dims, mode=mode, preSmoothing=pre, postSmoothing=post,
                        omega=omega, gamma=gamma, stencil=gsv.Stencil(list(values), list(offsets)))
     with gsv.HipGridData(p) as g:

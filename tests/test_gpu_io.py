@@ -161,6 +161,51 @@ def test_kernels_word_for_word(shape, layout):
                     src.assert_unchanged(what="export source " + what)
 
 
+# ---- the rows' non-temporal instance --------------------------------------------------------------------------------
+# The smallest level that selects k_io_rows<d, t, 1, 1> without a switch: exactly 2^25 points, unit-stride x and pitches
+# that allow 16-byte accesses; beside it the cached instance just below the threshold, whose rows of 4095 points in the
+# same pitch of 4096 end in one ragged 16-byte group. The external side is a contiguous [z][y][4096] tensor.
+NT_PITCH = 4096
+NT_SHAPES = {(4096, 64, 128): 1, (4095, 64, 128): 0}
+
+
+@pytest.mark.parametrize("dtype", [A.GS_IO_F64, A.GS_IO_F32], ids=["f64", "f32"])
+@pytest.mark.parametrize("shape", NT_SHAPES, ids=sid)
+def test_rows_at_the_nt_threshold(shape, dtype):
+    """Both directions at scale -0.375 in the default layout: import into a NaN-poisoned field (exactly the interior is
+    written), export of that field into sentinel storage; words equal to numpy's, the source unchanged."""
+    lib, nt, scale = gsv.io(), NT_SHAPES[shape], -0.375
+    nx, ny, nz = shape
+    assert (nx * ny * nz >= 1 << 25) == bool(nt) and (NT_PITCH - 1) * ny * nz < 1 << 25
+    npt = NPT[dtype]
+    s = (1, NT_PITCH, NT_PITCH * ny)
+    sabi = (A.i64 * 3)(*s)
+    lay = layouts(*shape)["default"]
+    fld = LayoutField(*shape, lay.ldy, lay.ldz, lay.phase_out)
+    L = fld.level(1.0 / (ny + 1))
+    for d in (A.GS_IO_IMPORT, A.GS_IO_EXPORT):
+        assert lib.gs_io_kernel(d, dtype, C.byref(L), sabi).decode() == f"k_io_rows<{d}, {dtype}, 1, {nt}>"
+    host = np.random.default_rng(5).uniform(-2.0, 2.0, (nz, ny, NT_PITCH)).astype(npt)  # [z][y][x]: all of it data
+    ext = torch.from_numpy(host).cuda()
+    fld.poison_all()
+    assert lib.gs_io_import(fld.ptr, C.byref(L), ext.data_ptr(), dtype, sabi, scale, st()) == 0
+    fld.assert_written_exactly(fld.interior_mask(), "import")
+    got = fld._box(fld.buf)[1:-1, 1:-1, 1:-1].cpu().numpy()
+    want = np.float64(scale) * host[:, :, :nx].astype(np.float64)
+    same(got, want, "import")
+    same(ext.cpu().numpy(), host, "import source")
+    del ext
+    # export what the import left: a field whose every word outside the interior is a NaN
+    fld.snapshot()
+    sent = np.full((nz, ny, NT_PITCH), SENTINEL[npt], dtype=IW[npt]).view(npt)
+    out = torch.from_numpy(sent).cuda()
+    assert lib.gs_io_export(fld.ptr, C.byref(L), out.data_ptr(), dtype, sabi, scale, st()) == 0
+    torch.cuda.synchronize()
+    sent[:, :, :nx] = (np.float64(scale) * want).astype(npt)
+    same(out.cpu().numpy(), sent, "export")
+    fld.assert_unchanged(what="export source")
+
+
 # ---- the driver ---------------------------------------------------------------------------------------------------
 def make_grid(kind, maxiter=3):
     if kind == "xy":

@@ -163,6 +163,30 @@ def test_pcg_dir_zmarch(sname, first, lid):
         f"k_pcg_dir_rb<{un}, {'true' if first else 'false'}>"
 
 
+# the z-march's chunk is pass_plan's (nz * tiles / 2048 in 4..32): BIG runs its minimum only. Two thin levels of
+# tests/test_gpu_rb_pass.py, shape: (chunk, blocks) — an odd chunk (the step whose results are discarded, in every
+# chunk) and the 32-plane cap, both with a last chunk of one plane
+THIN = {(3, 2, 14337): (7, 2049), (2, 3, 65537): (32, 2049)}
+
+
+@pytest.mark.parametrize("lid", ["default", "tight_odd"])
+@pytest.mark.parametrize("sname,first", [("unit", False), ("general", True)])
+@pytest.mark.parametrize("shape", THIN, ids=sid)
+def test_pcg_dir_zmarch_chunks(shape, sname, first, lid):
+    zc, blocks = THIN[shape]
+    values, offsets = STENCILS[sname]
+    S = gsv.Stencil(list(values), offsets).to_abi()
+    lay = layouts(*shape)[lid]
+    L = gsv.gs_level(*shape, lay.ldy, lay.ldz, 0, 1.0 / (shape[1] + 1))
+    # one x-y tile: the number of partials is the number of chunks, which only this chunk length gives
+    assert blocks == -(-shape[2] // zc) and len({-(-shape[2] // c) for c in (zc - 1, zc, zc + 1)}) == 3
+    assert kr().gs_pcg_dir_num_partials(C.byref(S), C.byref(L)) == blocks
+    un = "true" if sname == "unit" else "false"
+    assert kr().gs_pcg_dir_kernel(C.byref(S), C.byref(L), int(first)).decode() == \
+        f"k_pcg_dir_rb<{un}, {'true' if first else 'false'}>"
+    run_dir(shape, lid, sname, first)
+
+
 def test_pcg_dir_first_is_beta_zero_and_aliasing_is_refused():
     shape = (33, 17, 9)
     values, offsets = STENCILS["unit"]

@@ -142,13 +142,45 @@ def zslab_cases(n=30, seed=7):
     return out
 
 
-@pytest.mark.parametrize("case", zslab_cases(), ids=lambda c: f"z{c[0]}-{'x'.join(map(str, c[1]))}-r{c[2]}-m{c[3]}")
+def zslab_siblings(drawn):
+    """tests/test_gpu_fuzz.py's sibling rule: every drawn non-LINEAR case whose x or z axis is longer than y, with its
+    longest axis swapped into y (x before z on a tie), so that x = i h, h = 1 / (ny + 1), stays inside (0, 1] and the
+    non-linear right-hand side cannot overflow. The z axis keeps at least four planes per rank."""
+    out = []
+    for i, dims, nranks, mode, *rest in drawn:
+        if mode != 0 and max(dims[0], dims[2]) > dims[1]:
+            a = 0 if dims[0] >= dims[2] else 2
+            d = list(dims)
+            d[a], d[1] = d[1], d[a]
+            assert d[2] >= 4 * nranks, (i, d)
+            out.append((f"{i}y", tuple(d), nranks, mode, *rest))
+    return out
+
+
+def zslab_id(c):
+    return f"z{c[0]}-{'x'.join(map(str, c[1]))}-r{c[2]}-m{c[3]}"
+
+
+@pytest.mark.parametrize("case", zslab_cases(), ids=zslab_id)
 def test_zslab_random_vs_single(case):
     """Seeded random shapes, rank counts (2-5, uneven slabs), modes, smoothing counts and agglomeration
     thresholds: the loopback Z-slab solve against the single-GPU one, fields bit for bit."""
+    zslab_vs_single(case, finite=False)
+
+
+@pytest.mark.parametrize("case", zslab_siblings(zslab_cases()), ids=zslab_id)
+def test_zslab_sibling_vs_single(case):
+    """No case that compares nothing: the siblings' single-GPU history and field are wholly finite, asserted before
+    the comparison."""
+    zslab_vs_single(case, finite=True)
+
+
+def zslab_vs_single(case, finite):
     _, dims, nranks, mode, pre, post, min_points = case
     p = gsv.GridParams(maxiter=2, tol=0.0, gridDim=dims, mode=mode, preSmoothing=pre, postSmoothing=post)
     h1, v1 = single(p, 0, True)
+    if finite:
+        assert np.isfinite(h1).all() and np.isfinite(v1).all(), "the single-GPU result is not finite"
     hn, vn = loopback(p, nranks, min_points, 0, True)
     a, b = np.ascontiguousarray(vn[:, :, 1:-1]), np.ascontiguousarray(v1[:, :, 1:-1])
     assert a.tobytes() == b.tobytes() or np.array_equal(a, b, equal_nan=True)

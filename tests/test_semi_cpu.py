@@ -224,6 +224,19 @@ def test_trace_grid_is_refused(nranks, monkeypatch):
     assert rc == 1 and "XY needs a LINEAR grid" in err, err
 
 
+def test_header_exports_and_binding_agree():
+    from conftest import REPO
+    from test_abi import declared, exported
+    import os
+
+    names = set(declared(os.path.join(REPO, "include", "gpusolve_semi.h")))
+    assert names == {"gs_semi_level_stencil", "gs_restrict_xy", "gs_prolong_add_xy", "gs_residual_restrict_xy",
+                     "gs_residual_restrict_xy_chunk", "gs_semi_kernel", "gs_semi_launch_dry_run",
+                     "gs_semi_launch_record"}
+    assert {n for n in exported(A.SEMI_LIB) if n.startswith("gs_")} == names
+    assert names == set(A.SEMI_API)
+
+
 def test_python_names():
     assert (gsv.GS_COARSEN_XYZ, gsv.GS_COARSEN_XY, gsv.GS_SMOOTHER_AUTO) == (0, 1, 2)
     with pytest.raises(ValueError):

@@ -32,12 +32,24 @@ def axis_tables(n):
     pa = 1.0 - pt
     s = np.float64(m + 1) / np.float64(D)
     rlo, rcnt, rw = np.zeros(m + 2, np.int32), np.zeros(m + 2, np.int32), np.zeros((m + 2, 4))
-    for J in range(1, m + 1):
-        idx = [int(k) for k in range(1, n + 1) if pj[k] == J or (pj[k] == J - 1 and rem[k] > 0)]
-        assert 1 <= len(idx) <= 4 and idx == list(range(idx[0], idx[0] + len(idx))), (n, J, idx)
-        rlo[J], rcnt[J] = idx[0], len(idx)
-        for k, fi in enumerate(idx):
-            rw[J, k] = s * pa[fi] if pj[fi] == J else s * pt[fi]
+    # coarse J gathers the fine k with pj[k] == J (weight s * pa[k]) or pj[k] == J - 1 and rem[k] > 0 (s * pt[k]):
+    # all (J, k, weight) pairs at once, ascending in k within every J (a long axis has too many for a loop per J)
+    k = np.arange(1, n + 1, dtype=np.int64)
+    up = k[rem[1:n + 1] > 0]
+    J = np.concatenate([pj[k], pj[up] + 1])
+    fi = np.concatenate([k, up])
+    w = np.concatenate([s * pa[k], s * pt[up]])
+    keep = (J >= 1) & (J <= m)  # the coarse ring gathers nothing
+    J, fi, w = J[keep], fi[keep], w[keep]
+    order = np.lexsort((fi, J))
+    J, fi, w = J[order], fi[order], w[order]
+    first = np.searchsorted(J, np.arange(1, m + 1))
+    count = np.searchsorted(J, np.arange(1, m + 1), side="right") - first
+    assert ((count >= 1) & (count <= 4)).all(), n
+    slot = np.arange(J.size) - first[J - 1]
+    assert (fi == fi[first][J - 1] + slot).all(), n  # consecutive fine points
+    rlo[1:m + 1], rcnt[1:m + 1] = fi[first], count
+    rw[J, slot] = w
     return {"pj": pj.astype(np.int32), "pt": pt, "rlo": rlo, "rcnt": rcnt, "rw": rw}
 
 
